@@ -148,6 +148,36 @@ def pmc_counters(kernel_substr, argv, passes=PMC_PASSES, child_args=("--steps", 
     return out, None
 
 
+DUMP_BYTES = 64_000_000        # --dump-outputs: at most this much in all, .npy headers included
+
+
+def dump_outputs(out_dir, model, wl, loss):
+    """What the last timed step handed its caller, as out_dir/<name>.npy (float64): the surrogate loss(es) model(batch) returned,
+    the estimator's scalars, the walkers x and their local energies, and every parameter's gradient and value after the Adam
+    step.  When x and E_loc of all walkers would not fit DUMP_BYTES, a fixed sample of walkers (numpy seed 0, sorted, the same
+    for x and E_loc) stands for them; torch's generators are not touched, so the later legs see what they see without a dump."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([float(t.item()) for t in (loss if isinstance(loss, tuple) else (loss,))]),
+              "estimator": np.array([model.E, model.E_std] + ([model.F, model.F_std, model.S, model.S_analytical] if wl == "beta" else []))}
+    if wl == "beta":
+        arrays["logp_states_all"] = model.logp_states_all.detach().cpu().numpy()
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p.detach().cpu().numpy()
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad.detach().cpu().numpy()
+    x, eloc = model.x.detach(), model.Eloc.detach()
+    room = DUMP_BYTES - sum(a.nbytes for a in arrays.values()) - 1024 * (len(arrays) + 2)      # (1 KB per file for its header)
+    row = x[0].numel() * 8 + 8
+    if x.shape[0] * row > room:
+        keep = torch.as_tensor(np.sort(np.random.default_rng(0).choice(x.shape[0], room // row, replace=False)), device=x.device)
+        x, eloc = x[keep], eloc[keep]
+    arrays["x"], arrays["eloc"] = x.cpu().numpy(), eloc.cpu().numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -177,7 +207,12 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline.traffic = null)")
     ap.add_argument("--standalone-leg", action="store_true",
                     help="(child passes) run only the stand-alone HBM-bound kernels -- parity-mode Metropolis sweep, potential -- three times and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (rank 0; float64, at most 64 MB: "
+                         "a fixed sample of the walkers when all of them do not fit) -- to compare two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Launched bare (`python bench.py --gpus N`): this parent starts the N ranks itself -- before anything here has
@@ -252,6 +287,8 @@ def main():
         torch.cuda.synchronize()
         return
 
+    last_loss = []      # (--dump-outputs only) what model(batch) returned in the latest step
+
     def step():
         g = model(B_glob)
         opt.zero_grad()
@@ -260,6 +297,8 @@ def main():
         else:
             g.backward()
         opt.step()
+        if args.dump_outputs:
+            last_loss[:] = [g]
 
     def fence():
         if world > 1:
@@ -283,6 +322,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, wl, last_loss[0])
     prof, model.profile = model.profile, None
     E_head, Estd_head = model.E, model.E_std
     _v = gs.cnf.v_wrapper.v      # the headline's weights, for the CPU baseline (the later legs train them on)

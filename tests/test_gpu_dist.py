@@ -126,15 +126,23 @@ def test_rccl_single_rank_sweep_equals_plain_sweep():
 
 
 def _run_rccl(rank, world, port, B, out):
-    """One rank per GPU over nccl (= RCCL): the production collective path of fermiflow_amd/dist.py."""
+    """One rank per GPU over nccl (= RCCL): the production collective path of fermiflow_amd/dist.py.  With fewer GPUs than ranks
+    (the one-GPU test box) the ranks share cuda:0 and each names its own host (NCCL_HOSTID): RCCL refuses two ranks on one device
+    of one host, and as ranks of two hosts they meet over its socket transport on the loopback interface instead of xGMI."""
+    import datetime
     import torch.distributed as dist
     import __graft_entry__ as G
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     os.environ["FERMIFLOW_DIST_FORCE"] = "1"
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    dev = torch.device(f"cuda:{rank}")
+    ndev = torch.cuda.device_count()
+    if ndev < world:
+        os.environ["NCCL_HOSTID"] = f"fermiflow-test-rank-{rank}"
+        os.environ["NCCL_SOCKET_IFNAME"] = "lo"
+        os.environ["NCCL_IB_DISABLE"] = "1"
+    dev = torch.device(f"cuda:{rank % ndev}")
     torch.cuda.set_device(dev)
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=datetime.timedelta(seconds=180))
     model = G._model(dev, 3, 3, 2.0)
     torch.manual_seed(123)
     g = model(B)
@@ -145,11 +153,8 @@ def _run_rccl(rank, world, port, B, out):
 
 
 def test_two_ranks_over_rccl_equal_one_rank():
-    """test_two_ranks_equal_one_rank over RCCL, one GPU per rank -- the collective the 8-GPU bench uses, not
-    the gloo / CPU detour the one-GPU test box is limited to.  Skipped unless two devices are visible (RCCL refuses two ranks on one
-    GPU), so that the first multi-GPU box exercises it."""
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs (RCCL: one device per rank)")
+    """test_two_ranks_equal_one_rank over RCCL -- the collective the 8-GPU bench uses, not the gloo / CPU
+    detour.  One GPU per rank when two devices are visible; on a one-GPU box both ranks share it as ranks of two hosts (_run_rccl)."""
     B = 4096
     ctx = mp.get_context("spawn")
     mgr = ctx.Manager()
@@ -202,21 +207,22 @@ def test_bench_gpus_2_refuses_a_one_gpu_box_and_runs_two_ranks_over_gloo():
     assert weak["n_gpus"] == 2 and weak["scaling"] == "weak" and weak["config"]["global_walkers"] == 8192
 
 
-def test_eight_ranks_strong_scaling_dry_run():
-    """the first 8-GPU run should be boring.  bench.py --gpus 8 --scaling strong at the headline's global
-    batch (65 536 walkers, 8 192 per rank) with eight gloo ranks sharing the one GPU of the test box: the self-launch path, the
-    shard arithmetic, both estimator all-reduces and the rank-0 parameter sync at the real width -- E and E_std must equal the
-    one-rank values to reduction-order noise (the walkers are the same: Philox counters are global walker indices)."""
+def test_four_ranks_strong_scaling_dry_run():
+    """the first multi-GPU run should be boring.  bench.py --gpus 4 --scaling strong at the headline's global
+    batch (65 536 walkers, 16 384 per rank) with four gloo ranks sharing the one GPU of the test box: the self-launch path, the
+    shard arithmetic, both estimator all-reduces and the rank-0 parameter sync -- E and E_std must equal the one-rank values to
+    reduction-order noise (the walkers are the same: Philox counters are global walker indices).  Four ranks, not the eight of
+    the 8-GPU run: with this process and the launching bench.py that is as many processes holding the shared GPU as a test may."""
     if torch.cuda.device_count() >= 8:
         pytest.skip("written for a one-GPU box (the driver measures the real curve)")
     common = ["--steps", "2", "--warmup", "1", "--no-extras", "--walkers-per-gpu", "65536"]
     rc1, one, err1 = _bench(["--gpus", "1"] + common)
     assert rc1 == 0, err1[-2000:]
-    rc8, eight, err8 = _bench(["--gpus", "8", "--scaling", "strong"] + common, {"FF_BENCH_BACKEND": "gloo"}, timeout=900)
-    assert rc8 == 0, err8[-2000:]
-    assert eight["n_gpus"] == 8 and eight["scaling"] == "strong" and eight["config"]["global_walkers"] == 65536
-    assert abs(eight["E"] - one["E"]) < 1e-12 * abs(one["E"]), (eight["E"], one["E"])
-    assert abs(eight["E_std"] - one["E_std"]) < 1e-10 * one["E_std"]
+    rc4, four, err4 = _bench(["--gpus", "4", "--scaling", "strong"] + common, {"FF_BENCH_BACKEND": "gloo"}, timeout=900)
+    assert rc4 == 0, err4[-2000:]
+    assert four["n_gpus"] == 4 and four["scaling"] == "strong" and four["config"]["global_walkers"] == 65536
+    assert abs(four["E"] - one["E"]) < 1e-12 * abs(one["E"]), (four["E"], one["E"])
+    assert abs(four["E_std"] - one["E_std"]) < 1e-10 * one["E_std"]
 
 
 def test_ff_comm_single_rank_all_reduce():
