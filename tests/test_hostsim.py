@@ -977,3 +977,85 @@ def test_one_launch_estimator_and_schedule_with_mean():
             assert tab2[3] == tab[3] * 0.93 and tab2[0] == min(1.0, tab[0] * 1.02) and tab2[6] == min(1.0, tab[6] * 1.02)
             assert tab2[7] == tab[7] and tab2[9] == tab[9] and tab2[2] == tab[2]
             assert tab4[12] == tab[12] * 1.02 and tab4[20] == tab[20] * 1.02 and tab4[15] == tab[15] and tab4[3] == tab[3]
+
+
+# ------------------------------------------------------------------------------------------------ looping persistent grids
+# Counterparts of tests/test_gpu_geometry.py: the simulator reports 2 CUs, so the grids (4 workgroups per CU) loop at B of a
+# few hundred -- a state carried from one walker group to the next shows (and can be debugged) here without a GPU.
+def _looping_case(golden, nup, ndn, calls, seed):
+    from tests.common import assert_loops, kernel_families, looping_batch, probe_set
+    n = nup + ndn
+    fams = {}
+    for call in calls:
+        fams.update(kernel_families(call, n, 2, 2, hostsim=True))
+    B = looping_batch(fams)
+    assert_loops(fams, B)
+    P = probe_set(B, fams, seed=seed, nrand=4, edge_rounds=2)
+    eta, mu = net_arrays(golden["g5_gsvmc"], "z2_nt_")
+    return B, P, eta, mu, np.random.RandomState(seed).randn(B, n, 2)
+
+
+@pytest.mark.parametrize("nup,ndn", [(3, 3), (4, 3)])
+def test_looping_grids_give_each_walker_what_it_gets_alone(golden, nup, ndn):
+    """flow, local energy and adjoint at a B that loops every grid with a ragged last group: the probe walkers bit-identical
+    (outputs and step counts) to a batch of them alone; the adjoint with seeds exactly zero outside S has gx = 0 there and the
+    gp of the S-only call, and matches the oracle."""
+    B, P, eta, mu, z = _looping_case(golden, nup, ndn, ("flow", "eloc", "adjoint"), 3 + nup)
+    net = S.Net(eta, mu, table=True)
+    rt, at = 1e-9, 1e-11
+    cf, cs = np.full(B, -1, np.int32), np.full(len(P), -1, np.int32)
+    x, _ = S.cnf_generate(z, net, rtol=rt, atol=at, steps=cf)
+    xs, _ = S.cnf_generate(z[P], net, rtol=rt, atol=at, steps=cs)
+    np.testing.assert_array_equal(x[P], xs); np.testing.assert_array_equal(cf[P], cs)
+    cf, cs = np.full(B, -1, np.int32), np.full(len(P), -1, np.int32)
+    r = S.eloc(x, nup, ndn, net, 1.0, rtol=rt, atol=at, steps=cf)
+    rs = S.eloc(x[P], nup, ndn, net, 1.0, rtol=rt, atol=at, steps=cs)
+    for k in ("logp", "grad", "lap", "V", "eloc", "z", "dlogp", "glogp0"):
+        np.testing.assert_array_equal(r[k][P], rs[k], err_msg=k)
+    np.testing.assert_array_equal(cf[P], cs)
+    inS = np.zeros(B, bool); inS[P] = True
+    rng = np.random.RandomState(11)
+    a_z = np.where(inS[:, None, None], rng.randn(B, nup + ndn, 2), 0.0) / len(P)
+    a_d = np.where(inS, rng.randn(B), 0.0) / len(P)
+    cf, cs = np.full(B, -1, np.int32), np.full(len(P), -1, np.int32)
+    gx, gp, _ = S.cnf_adjoint(z, a_z, a_d, net, rtol=rt, atol=at, steps=cf)
+    gxs, gps, _ = S.cnf_adjoint(z[P], a_z[P], a_d[P], net, rtol=rt, atol=at, steps=cs)
+    assert not gx[~inS].any()
+    np.testing.assert_array_equal(gx[P], gxs); np.testing.assert_array_equal(cf[P], cs)
+    assert np.abs(gp - gps).max() <= 1e-12 * np.abs(gps).max()
+    onet = O.Net(eta, mu)
+    gxo, gpo, _ = O.cnf_adjoint(z[P], np.zeros(len(P)), a_z[P], a_d[P], onet, rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(gp, gpo, atol=2e-5 * np.abs(gpo).max())
+    np.testing.assert_allclose(gxs, gxo, atol=2e-5 * np.abs(gxo).max())
+    ref = O.eloc(x[P], nup, ndn, onet, 1.0, rtol=1e-10, atol=1e-12)
+    assert (np.abs(rs["eloc"] - ref["eloc"]) / np.abs(ref["eloc"])).max() < 1e-5
+    # energy-seeded entry: E_b = e_mean outside S makes those seeds exactly zero
+    k = np.where(inS, rng.randint(1, 257, size=B), 0)
+    e_mean, scale = 2.5, 2.0 ** -10
+    g0 = rng.randn(B, nup + ndn, 2)
+    gxe, gpe, _ = S.cnf_adjoint_energy(z, g0, e_mean + k / 64.0, e_mean, scale, net, rtol=rt, atol=at)
+    assert not gxe[~inS].any()
+    w = (k / 64.0) * scale
+    gxw, gpw, _ = S.cnf_adjoint(z[P], w[P, None, None] * g0[P], -w[P], net, rtol=rt, atol=at)
+    np.testing.assert_array_equal(gxe[P], gxw)
+    assert np.abs(gpe - gpw).max() <= 1e-12 * np.abs(gpw).max()
+
+
+@pytest.mark.parametrize("nup,ndn", [(3, 3)])
+def test_off_table_fallback_grids_loop(golden, nup, ndn):
+    """one walker far off the radial table at index B - 1 of a batch whose local-energy and adjoint fallback grids loop (the flow's
+    fallback is capped at 2048 workgroups, not by CU count: it loops only at GPU sizes, test_gpu_geometry.py): table net == exact
+    net, bit for bit, for the flow, the local energy and the adjoint."""
+    B, P, eta, mu, z = _looping_case(golden, nup, ndn, ("eloc_fb", "adj_fb"), 9)
+    z[B - 1, ::2, 0] += 17.0
+    z[B - 1, 1::2, 0] -= 17.0
+    tab, exact = S.Net(eta, mu, table=True), S.Net(eta, mu)
+    xt, _ = S.cnf_generate(z, tab); xe, _ = S.cnf_generate(z, exact)
+    np.testing.assert_array_equal(xt, xe)
+    rt, re = S.eloc(z, nup, ndn, tab, 2.0), S.eloc(z, nup, ndn, exact, 2.0)
+    for k in ("z", "dlogp", "grad", "lap", "eloc"):
+        np.testing.assert_array_equal(rt[k], re[k], err_msg=k)
+    rng = np.random.RandomState(4)
+    a_z, a_d = rng.randn(*z.shape) / B, rng.randn(B) / B
+    gxt, gpt, _ = S.cnf_adjoint(z, a_z, a_d, tab); gxe, gpe, _ = S.cnf_adjoint(z, a_z, a_d, exact)
+    np.testing.assert_array_equal(gxt, gxe); np.testing.assert_array_equal(gpt, gpe)
