@@ -1490,7 +1490,7 @@ static int launch_fwd(void* stream, const ff_fwd_args& a) {
 }
 
 // n >= 8 uses the two-lanes-per-direction local-energy kernel (measured, 32768 walkers: n = 8 6.5 -> 4.5 ms,
-// n = 10 48 -> 9.3 ms, n = 12 95 -> 14.7 ms); FF_NO_SPLIT=1 forces the one-lane-per-direction kernel (A/B testing)
+// n = 10 48 -> 9.3 ms, n = 12 95 -> 14.7 ms)
 template <int N, int D>
 static void launch_split(void* stream, const ff_fwd_args& a) {
   constexpr int G = FF_WAVE / (2 * N * D);

@@ -1,11 +1,17 @@
-// ff_dp5.h -- the Dormand-Prince 5(4) stage machine of the one-walker-per-workgroup ("wide") kernels, written once.
+// ff_dp5.h -- the Dormand-Prince 5(4) stage machine of the one-walker-per-workgroup ("wide") kernels.
+//
+// ff_dp5_consume: ff_wide_flow_kernel (ff_wide.hip), ff_wide_adjtab_kernel and ff_wide_adj_kernel (ff_adj_wide.h).
+// ff_dp5_consume2: ff_wide_eloc_kernel (ff_wide.hip; fp64 and fp32 J).
+// The several-walkers-per-wave forward kernels -- ff_ode_fwd_kernel and ff_eloc_split_kernel (ff_cnf_fwd.hip), ff_eloc_rows_kernel
+// (ff_eloc_rows.h), ff_eloc_mfma_kernel (ff_eloc_mfma.h) -- write the same five-vector bookkeeping inline, with wave-voted
+// decisions (ff_wave_or).
 //
 // Same rules as every fused integrator of this library (ff_ode.h: Hairer initial step or a warm start, RMS error norm over
 // the walker's own state, 0.9 err^-1/5 clamped to [0.2, 10], predictive bound, no growth right after a rejection) and the
 // same 5-vector storage as ff_ode_fwd_kernel: y, c0..c2 hold k0..k2 up to stage 3; once k3 is known the inputs of stages
 // 4, 5, the candidate y_new and the error accumulator c3 are formed and overwrite them.  An accepted step takes k6 as
 // the next k0 (FSAL); a rejected one re-evaluates f(y) in a "stage 0".
-// In these kernels ONE walker occupies the whole workgroup, so every decision is workgroup-uniform: no wave votes.
+// In the consume kernels ONE walker occupies the whole workgroup, so every decision is workgroup-uniform: no wave votes.
 //
 // Stage index s: -2 f(y) at the start, -1 the probe of the initial-step heuristic, 0 f(y) after a rejection, 1..6 the
 // stages of a step (6 = f(y_new), the error estimate and the accept / reject decision).
@@ -157,7 +163,8 @@ FF_D int ff_dp5_consume2(int s, ff_stepper& S, ff_dp5_ctl& C, YA& yA, TA* c0A, T
                          double* yB, double* c0B, double* c1B, double* c2B, C3B& c3B, const double* outB, WB wgtB, G gsum) {
   const double h = S.h, rtol = C.rtol, atol = C.atol;
   const TA hA = (TA)h, rtA = (TA)rtol, atA = (TA)atol, wA = (TA)wA_;
-  constexpr bool ACC0 = C3A::in_lds;      // from stage 4 on the error accumulator lives in c0 (see there)
+  // from stage 4 on the error accumulator of a segment lives in its c0 where its c3 is in LDS (see there)
+  constexpr bool ACC0 = C3A::in_lds, ACC0B = C3B::in_lds;
   if (s == -2) {
     TA qa0 = 0, qa1 = 0;
 #pragma unroll
@@ -261,9 +268,9 @@ FF_D int ff_dp5_consume2(int s, ff_stepper& S, ff_dp5_ctl& C, YA& yA, TA* c0A, T
     for (int v = 0; v < NB; v++) {
       c1B[v] = fma(h * FF_A54, outB[v], c1B[v]);
       c2B[v] = fma(h * FF_B4, outB[v], c2B[v]);
-      if constexpr (ACC0) c0B[v] = fma(h * FF_E4, outB[v], c3B[v]);
+      if constexpr (ACC0B) c0B[v] = fma(h * FF_E4, outB[v], c3B[v]);
       else c3B[v] = fma(h * FF_E4, outB[v], c3B[v]);
-      if constexpr (PIN) { FF_OPAQUE(c1B[v]); FF_OPAQUE(c2B[v]); if constexpr (ACC0) FF_OPAQUE(c0B[v]); }
+      if constexpr (PIN) { FF_OPAQUE(c1B[v]); FF_OPAQUE(c2B[v]); if constexpr (ACC0B) FF_OPAQUE(c0B[v]); }
     }
     return 5;
   }
@@ -278,9 +285,9 @@ FF_D int ff_dp5_consume2(int s, ff_stepper& S, ff_dp5_ctl& C, YA& yA, TA* c0A, T
 #pragma unroll
     for (int v = 0; v < NB; v++) {
       c2B[v] = fma(h * FF_B5, outB[v], c2B[v]);
-      if constexpr (ACC0) c0B[v] = fma(h * FF_E5, outB[v], c0B[v]);
+      if constexpr (ACC0B) c0B[v] = fma(h * FF_E5, outB[v], c0B[v]);
       else c3B[v] = fma(h * FF_E5, outB[v], c3B[v]);
-      if constexpr (PIN) { FF_OPAQUE(c2B[v]); if constexpr (ACC0) FF_OPAQUE(c0B[v]); }
+      if constexpr (PIN) { FF_OPAQUE(c2B[v]); if constexpr (ACC0B) FF_OPAQUE(c0B[v]); }
     }
     return 6;
   }
@@ -295,7 +302,7 @@ FF_D int ff_dp5_consume2(int s, ff_stepper& S, ff_dp5_ctl& C, YA& yA, TA* c0A, T
   double pe = (double)qa;
 #pragma unroll
   for (int v = 0; v < NB; v++) {
-    const double e = fma(h * FF_E6, outB[v], ACC0 ? c0B[v] : (double)c3B[v]);
+    const double e = fma(h * FF_E6, outB[v], ACC0B ? c0B[v] : (double)c3B[v]);
     const double t = e * wgtB(v) * ff_rcp(fma(fmax(fabs(yB[v]), fabs(c2B[v])), rtol, atol));
     pe = fma(t, t, pe);
   }
