@@ -46,13 +46,13 @@ FF_D double ff_ho3d_logabsdet(int ns, const int* __restrict__ orb, const double*
       }
     const double piv = A[c * ns + c];
     acc += log(fabs(piv));
-    if (!deriv) {
+    if (!deriv) {   // (a zero pivot: det = 0 and the rest of the column is zero, nothing to eliminate -- LAPACK's getf2)
       for (int r = c + 1; r < ns; r++) {
-        const double f = A[r * ns + c] / piv;
+        const double f = piv != 0.0 ? A[r * ns + c] / piv : 0.0;
         for (int j = c + 1; j < ns; j++) A[r * ns + j] = A[r * ns + j] - f * A[c * ns + j];
       }
     } else {
-      const double ip = 1.0 / piv;
+      const double ip = piv != 0.0 ? 1.0 / piv : 0.0;
       for (int j = 0; j < ns; j++) { A[c * ns + j] *= ip; Inv[c * ns + j] *= ip; }
       for (int r = 0; r < ns; r++) {
         if (r == c) continue;
@@ -176,10 +176,14 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
   // samplers of ff_walkers.hip), phi_j = gauss * prod_c h_{deg_j,c}(x_c).  LU with partial pivoting without moving rows; the
   // pivot of a column is found by ONE 32-bit maximum over the group's 16 lanes (DPP): key = |entry| rounded to float with the lane
   // index in the low four bits (equal keys: the lower lane) -- a pivot that is within 2^-19 of the largest entry instead of the
-  // largest changes the rounding of log|det|, not its value.  |det| is the product of the pivots (one log per determinant).
-  // detprod(xx, true): the product of the pivots of the species' Slater matrix, the entries with their Gaussians; (xx, false): of its
-  // polynomial part h_nx(x) h_ny(y) [h_nz(z)] alone (the Gaussian of a row factors out of the determinant: the Philox-fed chain)
-  auto detprod = [&](const double* xx, bool with_gauss) -> double {
+  // largest changes the rounding of log|det|, not its value.  A nonzero entry keys above every exact zero (entries below the float
+  // range would round to key 0), and a zero pivot is LAPACK's: det = 0, the column is not eliminated (the rest of it is zero).
+  // |det| is the product of the pivots (one log per determinant).
+  // detprod(xx, true, &e): the product of the pivots of the species' Slater matrix, the entries with their Gaussians, as a mantissa
+  // in [1/2, 1) and its power of two in e (the product of the Gaussians leaves the double range in the tail: as ff_lu_absdet_reg);
+  // (xx, false): of its polynomial part h_nx(x) h_ny(y) [h_nz(z)] alone, unscaled (the Gaussian of a row factors out of the
+  // determinant: the Philox-fed chain)
+  auto detprod = [&](const double* xx, bool with_gauss, int* e2) -> double {
     double A[NS];
     double gs = 1.0;
     if (with_gauss) { if constexpr (D == 2) gs = ff_gauss2d(xx[0], xx[1]); else gs = ff_gauss3d(xx); }
@@ -217,12 +221,15 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
       A[j] = v;
     }
     double prod = 1.0;
+    int ex = 0;
     bool used = !mine;
 #pragma unroll
     for (int c = 0; c < NS; c++) {
       if (c >= nsmax) break;        // (kernel-uniform)
       const bool act = c < ns;      // (uniform within the group)
-      unsigned key = (!used && act) ? ((__float_as_uint((float)fabs(A[c])) & ~15u) | (unsigned)(15 - r)) : 0u;
+      unsigned kb = __float_as_uint((float)fabs(A[c])) & ~15u;
+      kb = (A[c] != 0.0 && kb == 0u) ? 16u : kb;
+      unsigned key = (!used && act) ? (kb | (unsigned)(15 - r)) : 0u;
       {
         unsigned o = (unsigned)__builtin_amdgcn_mov_dpp((int)key, 0xB1, 0xF, 0xF, true); key = o > key ? o : key;      // lane ^ 1
         o = (unsigned)__builtin_amdgcn_mov_dpp((int)key, 0x4E, 0xF, 0xF, true); key = o > key ? o : key;               // lane ^ 2
@@ -232,6 +239,7 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
       const int who = 15 - (int)(key & 15u);
       const double piv = ff_lane_read(A[c], (lane & ~15) | who);
       if (act) prod *= piv;
+      if (e2) { int e; prod = frexp(prod, &e); ex += e; }
       const bool ispiv = act && who == r && !used;
       if (ispiv) {
 #pragma unroll
@@ -239,8 +247,8 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
         used = true;
       }
       __syncthreads();
-      if (act && !used) {
-        const double f = A[c] * ff_rcp(piv);
+      if (act && !used) {     // (an entry equal to the pivot -- a row identical to the pivot row -- eliminates with exactly 1)
+        const double f = piv == 0.0 ? 0.0 : (A[c] == piv ? 1.0 : A[c] * ff_rcp(piv));
 #pragma unroll
         for (int j = 0; j < NS; j++) { if (j > c) A[j] = fma(-f, s_row[c & 1][grp][j], A[j]); }
       }
@@ -248,9 +256,16 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
       // the barrier of column c + 1, which every reader of column c reaches only after its reads)
     }
     __syncthreads();      // (the next call's first column writes buffer 0 again)
+    if (e2) *e2 = ex;
     return prod;
   };
-  auto logabsdet = [&](const double* xx) -> double { return log(fabs(detprod(xx, true))); };
+  // log|det| = log of the product where it is a normal double (the bits of the unscaled product), else log|mantissa| + e ln 2
+  auto logabsdet = [&](const double* xx) -> double {
+    int e;
+    const double m = fabs(detprod(xx, true, &e));
+    const bool normal = e >= -1021 && e <= 1024;
+    return log(normal ? ldexp(m, e) : m) + (normal ? 0.0 : (double)e * 0.69314718055994531);
+  };
   // log p of the walker = 2 (log|det up| + log|det down|): the two groups of a walker exchange their sums
   auto logprob = [&](const double* xx) -> double {
     const double mysum = logabsdet(xx);
@@ -316,7 +331,7 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
       return mine ? t : 0.0;
     };
     auto polyprod2 = [&](const double* xx) -> double {      // (P_up P_dn)^2
-      const double mp = detprod(xx, false), pp = mp * ff_lane_read(mp, lane ^ 16);
+      const double mp = detprod(xx, false, nullptr), pp = mp * ff_lane_read(mp, lane ^ 16);
       return pp * pp;
     };
     if (g0 != nullptr) {

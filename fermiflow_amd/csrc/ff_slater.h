@@ -66,8 +66,13 @@ FF_D void ff_orbital(int k, double x, double y, double gauss /* pi^-1/2 exp(-r^2
 }
 
 FF_D double ff_gauss2d(double x, double y) { return FF_PI_SQRT_INV * exp(-0.5 * (x * x + y * y)); }
-// same, with the in-house exp (argument clamped: exp(-708) is already a denormal-free 3e-308)
-FF_D double ff_gauss2d_fast(double x, double y) { return FF_PI_SQRT_INV * ff_exp(fmax(-0.5 * (x * x + y * y), -708.0)); }
+// same, with the in-house exp (argument clamped: exp(-708) is already a denormal-free 3e-308).  A NaN coordinate gives NaN, as
+// exp does: fmax would turn it into the clamp, and a NaN walker whose orbitals ignore that coordinate would get a finite row.
+FF_D double ff_gauss2d_fast(double x, double y) {
+  const double a = -0.5 * (x * x + y * y);
+  const double gs = FF_PI_SQRT_INV * ff_exp(fmax(a, -708.0));
+  return a == a ? gs : a;
+}
 
 // --------------------------------------------------------------------------------------------------
 // Register-resident log|det| for compile-time NS (MCMC hot loop).  The normalised Hermite function of degree n
@@ -176,10 +181,17 @@ FF_D double ff_inv_small(const double (&A)[NS][NS], double (&Ai)[NS][NS]) {
 
 // nx/ny: the orbitals' Hermite degrees, decoded once by the caller (ff_orb_decode) outside its step loop;
 // md: a wave-uniform upper bound of those degrees.
-// |det D| of a register-resident NS x NS matrix (destroyed): LU with partial pivoting, the product of the pivots
+// |det D| of a register-resident NS x NS matrix (destroyed): LU with partial pivoting, the product of the pivots.
+// A zero pivot is LAPACK's getf2: det = 0 and the column is not eliminated (the pivot is the largest |entry|, so the rest of
+// the column is zero too) -- no 0 * (1 / 0) = NaN that would reach every later pivot.  Identical rows (coincident particles of one
+// species) eliminate to an exactly zero row, so such a determinant is exactly 0 as in exact arithmetic.
+// e2 != null: the running product is kept as a mantissa in [1/2, 1) and the power of two goes to *e2, |det| = result * 2^*e2
+// (the product of NS pivots that carry their rows' Gaussians leaves the double range in the tail of the density).  Scaling by
+// powers of two is exact, so the mantissa has the bits of the plain product wherever that product is a normal number.
 template <int NS>
-FF_D double ff_lu_absdet_reg(double (&D)[NS][NS]) {
+FF_D double ff_lu_absdet_reg(double (&D)[NS][NS], int* e2 = nullptr) {
   double prod = 1.0;
+  int ex = 0;
 #pragma unroll
   for (int c = 0; c < NS; c++) {
     int p = c;
@@ -201,19 +213,29 @@ FF_D double ff_lu_absdet_reg(double (&D)[NS][NS]) {
     }
     double piv = D[c][c];
     prod *= fabs(piv);
-    double ip = 1.0 / piv;
+    if (e2) { int e; prod = frexp(prod, &e); ex += e; }
+    const double ip = piv != 0.0 ? 1.0 / piv : 0.0, one = piv != 0.0 ? 1.0 : 0.0;
 #pragma unroll
     for (int r = c + 1; r < NS; r++) {
-      double f = D[r][c] * ip;
+      const double f = D[r][c] == piv ? one : D[r][c] * ip;   // a row equal to the pivot row's leading entry: exactly 1
+      // (piv * (1 / piv) may round to 1 - 2^-53, and two identical rows would then leave a rounding residue instead of a zero row)
 #pragma unroll
       for (int j = c + 1; j < NS; j++) D[r][j] = fma(-f, D[c][j], D[r][j]);
     }
   }
+  if (e2) *e2 = ex;
   return prod;
 }
-// log|det D|: one log per determinant (NS <= 6: no over/underflow of the product)
+// log|det D|: one log per determinant, of mantissa * 2^e.  Where |det| is a normal double the log is taken of |det| itself (the
+// bits of the unscaled product); below or above the normal range, log(mantissa) + e ln 2.  A zero pivot gives exactly -inf, a
+// NaN entry NaN.
 template <int NS>
-FF_D double ff_lu_logabsdet_reg(double (&D)[NS][NS]) { return ff_log(ff_lu_absdet_reg<NS>(D)); }
+FF_D double ff_lu_logabsdet_reg(double (&D)[NS][NS]) {
+  int e;
+  const double m = ff_lu_absdet_reg<NS>(D, &e);
+  const bool normal = e >= -1021 && e <= 1024;     // mantissa in [1/2, 1): m 2^e is then a normal double
+  return ff_log(normal ? ldexp(m, e) : m) + (normal ? 0.0 : (double)e * 0.69314718055994531);
+}
 
 // det D up to its sign, for the ratio test of the Philox-fed Metropolis kernels: closed form up to 3 x 3, pivoted LU beyond
 template <int NS>
@@ -309,15 +331,15 @@ FF_D double ff_slater_general(int ns, const int* __restrict__ orb, const double*
       }
     double piv = A[c * ns + c];
     acc += log(fabs(piv));
-    if (!T) {  // value only: plain elimination below the pivot
-      double ip = 1.0 / piv;
+    if (!T) {  // value only: plain elimination below the pivot (a zero pivot: det = 0, nothing to eliminate, as LAPACK)
+      const double ip = piv != 0.0 ? 1.0 / piv : 0.0, one = piv != 0.0 ? 1.0 : 0.0;
       for (int r = c + 1; r < ns; r++) {
-        double f = A[r * ns + c] * ip;
+        const double f = A[r * ns + c] == piv ? one : A[r * ns + c] * ip;    // (identical rows: exactly 1, as ff_lu_absdet_reg)
         for (int j = c + 1; j < ns; j++) A[r * ns + j] = fma(-f, A[c * ns + j], A[r * ns + j]);
       }
       continue;
     }
-    double ip = 1.0 / piv;
+    double ip = piv != 0.0 ? 1.0 / piv : 0.0;
     for (int j = 0; j < ns; j++) { A[c * ns + j] *= ip; Inv[c * ns + j] *= ip; }
     for (int r = 0; r < ns; r++) {
       if (r == c) continue;
@@ -392,11 +414,11 @@ FF_D double ff_slater_fixed(const int* __restrict__ orb, const double* x, double
     }
     const double piv = A[c * NS + c];
     acc += log(fabs(piv));
-    const double ip = 1.0 / piv;
+    const double ip = piv != 0.0 ? 1.0 / piv : 0.0, one = piv != 0.0 ? 1.0 : 0.0;
     if constexpr (!DERIV) {   // value only: plain elimination below the pivot (as ff_slater_general without T)
 #pragma unroll
       for (int r = c + 1; r < NS; r++) {
-        const double f = A[r * NS + c] * ip;
+        const double f = A[r * NS + c] == piv ? one : A[r * NS + c] * ip;
 #pragma unroll
         for (int j = c + 1; j < NS; j++) A[r * NS + j] = fma(-f, A[c * NS + j], A[r * NS + j]);
       }

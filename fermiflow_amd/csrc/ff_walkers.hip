@@ -128,7 +128,10 @@ ff_mcmc_kernel(int64_t B, int nup_rt, int ndn_rt, const int* __restrict__ tab_up
         }
     }
     double nl = ff_logprob_value<NU, ND>(nup, ndn, ou, od, nx, md);
-    // p = exp(new_logp - logp) with torch's edge semantics: NaN stays NaN (rejects), -inf gives exactly 0
+    // p = exp(new_logp - logp) with torch's edge semantics: NaN stays NaN (rejects: a NaN walker, or -inf - -inf when a singular
+    // walker proposes another singular one), -inf gives exactly 0 (rejects), +inf (a walker with log p = -inf, e.g. every particle
+    // at the origin, proposing a regular one) accepts.  The clamped exponential gives e^708 for dlp >= 708, which every u < 1
+    // accepts, and 0 below -708, where torch's p is a denormal that only u == 0 exactly (a 2^-53 event) would accept.
     const double dlp = nl - logp;
     double p = exp(0.0);
     if constexpr (FIXED) p = !(dlp == dlp) ? dlp : (dlp < -708.0 ? 0.0 : ff_exp(fmin(dlp, 708.0)));

@@ -143,7 +143,7 @@ static jet JN(orbital3d)(int k, jet x, jet y, jet z) {
 }
 
 /* log|det D|, D[i][j] = phi_{orb[j]}(r_i)  (src/slater.py:28-36); LU with partial pivoting by
- * |value| as LAPACK getrf does behind torch.slogdet; logabsdet = sum log|U_ii|.  d = 2: HO2D, d = 3: HO3D. */
+ * |value| as LAPACK getrf does behind torch.slogdet; logabsdet = sum log|U_ii|, -inf at an exactly zero pivot.  d = 2: HO2D, d = 3: HO3D. */
 static jet JN(slater_logabsdet_d)(int n, int d, const int* orb, const jet* xy /* n*d */) {
   jet D[FFO_MAXN * FFO_MAXN];
   for (int i = 0; i < n; i++)
@@ -157,6 +157,7 @@ static jet JN(slater_logabsdet_d)(int n, int d, const int* orb, const jet* xy /*
     if (p != c) for (int j = 0; j < n; j++) { jet t = D[c * n + j]; D[c * n + j] = D[p * n + j]; D[p * n + j] = t; }
     jet piv = D[c * n + c];
     acc = JN(jadd)(acc, JN(jlogabs)(piv));
+    if (piv.v == 0.0) continue;   /* getf2: a zero pivot is det = 0, the column (all zero below it) is not eliminated */
     for (int r = c + 1; r < n; r++) {
       jet f = JN(jdiv)(D[r * n + c], piv);
       for (int j = c + 1; j < n; j++) D[r * n + j] = JN(jsub)(D[r * n + j], JN(jmul)(f, D[c * n + j]));

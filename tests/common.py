@@ -1,5 +1,6 @@
 """Helpers shared by the oracle, hostsim and GPU parity tests."""
 import hashlib
+import os
 
 import numpy as np
 import torch
@@ -45,6 +46,94 @@ GSVMC_PG = ["cnf.v_wrapper.v.eta.fc1.weight", "cnf.v_wrapper.v.eta.fc1.bias", "c
 def gsvmc_param_grads(G, name, use_mu=True):
     keys = GSVMC_PG if use_mu else GSVMC_PG[:3]
     return np.concatenate([G[f"{name}_pg_{k}"] for k in keys])
+
+
+
+# ---- sampler edge cases: tests/golden/g8_sampler_edges.npz (make_golden.py edges) -------------------------------------------
+# (loaded here, not in conftest.py's `golden` fixture: the edge tests bring their own module-level fixture)
+EDGE_SHAPES = [(2, 1), (3, 3), (6, 0), (6, 6), (4, 3), (10, 0)]     # log p probes, d = 2
+EDGE_SHAPES3D = [(4, 3), (10, 10)]                                  # d = 3
+EDGE_CHAINS = ["c3_3", "c6_0", "c2_1"]                              # crafted chains, d = 2 ("c3d4_3": d = 3)
+_G8 = {}
+
+
+def sampler_edges():
+    if not _G8:
+        with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g8_sampler_edges.npz")) as z:
+            _G8.update({k: z[k] for k in z.files})
+    return _G8
+
+
+def edge_chain(G, name):
+    """nup, ndn, g0, g, u, accept (steps, B), and the reference's final x, log p and initial log p of a g8 chain"""
+    nup, ndn, dim, B, steps = (int(v) for v in G[name + "_cfg"])
+    accept = np.unpackbits(G[name + "_accept"])[:steps * B].reshape(steps, B)
+    return (nup, ndn, G[name + "_g0"], G[name + "_g"].astype(np.float64), G[name + "_u"].astype(np.float64), accept,
+            G[name + "_x"], G[name + "_logp"], G[name + "_logp0"])
+
+
+def assert_edge_logp(lp, ref, rtol=1e-12):
+    """-inf exactly where the reference has -inf (a zero column), NaN where it has NaN, the rest to rtol"""
+    lp, ref = np.asarray(lp), np.asarray(ref)
+    assert (np.isneginf(lp) == np.isneginf(ref)).all(), (lp, ref)
+    assert (np.isnan(lp) == np.isnan(ref)).all(), (lp, ref)
+    f = np.isfinite(ref)
+    np.testing.assert_allclose(lp[f], ref[f], rtol=rtol, atol=0)
+
+
+def bits_equal(a, b):
+    """bit-identical float64 arrays (NaNs included)"""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and (a.view(np.uint64) == b.view(np.uint64)).all()
+
+
+def coincident_chains(nup, ndn, B, steps, dim=2, seed=0):
+    """Walkers with identical rows in a Slater matrix, and crafted noise (g0, g, u):
+      0: particles 0 and 1 (spin up) coincident, their proposals identical at every step -> the pair stays together;
+      1: the same pair, ordinary proposals -> the first one separates it;
+      2, 3: particles 0, 1, 2 coincident (nup >= 3; else another pair), kept together / separated;
+      4: a coincident pair in the down species (ndn >= 2; else in the up species), kept together;
+      the rest: ordinary walkers.
+    The determinant of a matrix with two equal rows is 0: log p = -inf in exact arithmetic, and the kernels and the oracle
+    compute it so (the reference returns a finite value that depends on LAPACK's rounding).  A chain whose pair stays
+    together never accepts (p = exp(-inf - -inf) = NaN); one whose first proposal separates it accepts step 1 (p = +inf)."""
+    rng = np.random.default_rng(seed)
+    n = nup + ndn
+    g0 = rng.standard_normal((B, n, dim)); g = rng.standard_normal((steps, B, n, dim)); u = rng.random((steps, B))
+    trip = [0, 1, 2] if nup >= 3 else [0, 1]
+    groups = {0: [0, 1], 1: [0, 1], 2: trip, 3: trip, 4: [nup, nup + 1] if ndn >= 2 else [nup - 2, nup - 1]}
+    for b, idx in groups.items():
+        g0[b, idx] = g0[b, idx[0]]
+        if b in (0, 2, 4):
+            g[:, b, idx] = g[:, b, idx[0]][:, None]
+    kept, separated = np.array([0, 2, 4]), np.array([1, 3])
+    return g0, g, u, kept, separated
+
+
+def special_starts(nup, ndn, B, positions, dim=2, seed=0):
+    """Ordinary normal walkers (B, n, dim) with special ones at `positions`, cycling through: all particles at the origin,
+    all on the first axis, all on the second axis, a spiral at radius 16, 22 or 30, one NaN coordinate, a coincident
+    pair (particles 0 and 1).  Returns the walkers and the same walkers with the special ones replaced by ordinary ones."""
+    rng = np.random.default_rng(seed)
+    n = nup + ndn
+    x = rng.standard_normal((B, n, dim))
+    plain = x.copy()
+    k = np.arange(n)
+    for i, b in enumerate(positions):
+        kind = i % 8
+        if kind == 0:
+            x[b] = 0.0
+        elif kind in (1, 2):
+            x[b] = 0.0; x[b, :, kind - 1] = np.linspace(-1.3, 1.7, n)
+        elif kind in (3, 4, 5):
+            r = (16.0, 22.0, 30.0)[kind - 3] * (1 + 0.1 * k / n)      # (distinct radii: see make_golden.edge_probes)
+            t = 2 * np.pi * (k + 0.37) / n
+            x[b] = 0.0; x[b, :, 0] = r * np.cos(t); x[b, :, 1] = r * np.sin(t)
+        elif kind == 6:
+            x[b, n - 1, 0] = np.nan
+        else:
+            x[b, 1] = x[b, 0]
+    return x, plain
 
 
 # ---- GPU-side helpers (fermiflow_amd is imported lazily: the CPU suite imports this module too)

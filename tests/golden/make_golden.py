@@ -3,7 +3,7 @@
 /root/reference through ref_shim.py) on seeded inputs.
 
 Run in the build container only:   python tests/golden/make_golden.py [group ...]
-Groups: mcmc slater backflow cnf gsvmc betavmc d3   (default: all)
+Groups: mcmc slater backflow cnf gsvmc betavmc d3 edges   (default: all)
 
 Every fixture stores inputs and the reference's outputs; no reference source text is stored.
 Reference call sites are cited next to each group.
@@ -506,7 +506,105 @@ def g_3d(R_unused):
     np.savez_compressed(path, **out)
 
 
-GROUPS = dict(mcmc=g_mcmc, slater=g_slater, backflow=g_backflow, cnf=g_cnf, gsvmc=g_gsvmc, betavmc=g_betavmc, d3=g_3d)
+# ---------------------------------------------------------------------------------------------
+EDGE_SHAPES = ((2, 1), (3, 3), (6, 0), (6, 6), (4, 3), (10, 0))
+EDGE_RADII = (8.0, 12.0, 16.0, 22.0, 30.0)
+
+
+def edge_probes(n, dim):
+    """Crafted walkers (P, n, dim): all particles at the origin; all on the first axis; all on the second axis; then one spiral
+    (d = 2: around the origin, d = 3: seeded directions) of distinct positions per radius of EDGE_RADII, the radii of its particles
+    spread over r (1 + [0, 0.1)) (d = 3: r (1 + [0, 0.2)); beyond r = 37 the Gaussian is below the double range).  No two particles coincide (identical rows are rank-deficient only up to LAPACK's rounding, and
+    the reference's answer there is noise, not a target), and no two share a radius (on a circle h_2(x) + h_2(y) is a multiple of
+    h_0, a column dependence that is exact only in exact arithmetic)."""
+    xs = [np.zeros((n, dim))]
+    for ax in (0, 1):
+        a = np.zeros((n, dim)); a[:, ax] = np.linspace(-1.3, 1.7, n) + 0.05 * ax; xs.append(a)
+    k = np.arange(n)
+    for r0 in EDGE_RADII:
+        r = (r0 * (1 + (0.1 if dim == 2 else 0.2) * k / n))[:, None]
+        t = 2 * np.pi * (k + 0.37) / n
+        if dim == 2:
+            xs.append(r * np.stack([np.cos(t), np.sin(t)], axis=-1))
+        else:
+            v = np.random.default_rng(int(r0)).standard_normal((n, 3))       # (seeded directions: a spiral is ill-conditioned at 10 x 10)
+            xs.append(r * v / np.linalg.norm(v, axis=-1, keepdims=True))
+    return np.stack(xs)
+
+
+def edge_starts(n, dim, B, rng):
+    """Starting walkers (B, n, dim) of the crafted chains: 0 origin, 1 first axis, 2 second axis, 3..5 rings at r = 16, 22, 30,
+    6 one NaN coordinate, the rest ordinary (normal) walkers.  Every start with log p = -inf accepts its first proposal."""
+    x = rng.standard_normal((B, n, dim))
+    P = edge_probes(n, dim)
+    x[0], x[1], x[2] = P[0], P[1], P[2]
+    x[3], x[4], x[5] = P[3 + EDGE_RADII.index(16.0)], P[3 + EDGE_RADII.index(22.0)], P[3 + EDGE_RADII.index(30.0)]
+    x[6, n - 1, 0] = np.nan
+    return x
+
+
+def replay_from(R, bd, up, dn, x0, gs, us, tau=0.1):
+    """The loop of FreeFermion.sample (src/base_dist.py:63-70) statement by statement from the walkers x0 with the noise
+    gs (S, B, n, d), us (S, B) given; log_prob is the reference's."""
+    torch = R.torch
+    x = torch.from_numpy(x0.copy())
+    logp = bd.log_prob(up, dn, x)
+    logp0 = logp.clone()
+    acc = []
+    for s in range(len(gs)):
+        new_x = x + tau * torch.from_numpy(gs[s])
+        new_logp = bd.log_prob(up, dn, new_x)
+        p = torch.exp(new_logp - logp)
+        a = torch.from_numpy(us[s]) < p
+        x[a] = new_x[a]; logp[a] = new_logp[a]
+        acc.append(a.numpy().copy())
+    return logp0.numpy(), np.stack(acc), x.numpy().copy(), logp.numpy().copy()
+
+
+def g_edges(R):
+    """Edge semantics of FreeFermion.log_prob and .sample (src/base_dist.py:49-71) at crafted walkers: exactly singular Slater
+    matrices (a zero column: every particle at the origin or on an axis -> log p = -inf, and a chain started there accepts its
+    first proposal, p = exp(+inf)), the far tail (log p down to about -10^4, where the product of the rows' Gaussians leaves the
+    double range) and a NaN walker (never accepts).  Inputs and the reference's outputs only."""
+    torch = R.torch
+    ho = R.orbitals.HO2D()
+    bd = R.base_dist.FreeFermion()
+    out = {"radii": np.array(EDGE_RADII)}
+    for nup, ndn in EDGE_SHAPES:                                                  # log p probes, d = 2
+        tag = f"p{nup}_{ndn}"
+        x = edge_probes(nup + ndn, 2)
+        out[tag + "_x"] = x
+        out[tag + "_logp"] = bd.log_prob(ho.orbitals[:nup], ho.orbitals[:ndn], torch.from_numpy(x)).numpy()
+    orbs3, _, _ = ho3d_closures(R)
+    for nup, ndn in ((4, 3), (10, 10)):                                           # d = 3
+        tag = f"p3d{nup}_{ndn}"
+        x = edge_probes(nup + ndn, 3)
+        out[tag + "_x"] = x
+        out[tag + "_logp"] = bd.log_prob(tuple(orbs3[:nup]), tuple(orbs3[:ndn]), torch.from_numpy(x)).numpy()
+    chains = {"c3_3": (3, 3, 2, 16, 20, 41), "c6_0": (6, 0, 2, 16, 20, 42), "c2_1": (2, 1, 2, 16, 20, 43),
+              "c3d4_3": (4, 3, 3, 8, 20, 44)}
+    for name, (nup, ndn, dim, B, steps, seed) in chains.items():
+        rng = np.random.default_rng(seed)
+        n = nup + ndn
+        x0 = edge_starts(n, dim, B, rng)
+        # (noise values exact in float32 and stored so: half the file; the chain runs on them as float64)
+        gs = rng.standard_normal((steps, B, n, dim)).astype(np.float32); us = rng.random((steps, B)).astype(np.float32)
+        up, dn = (tuple(orbs3[:nup]), tuple(orbs3[:ndn])) if dim == 3 else (ho.orbitals[:nup], ho.orbitals[:ndn])
+        logp0, acc, x, logp = replay_from(R, bd, up, dn, x0, gs.astype(np.float64), us.astype(np.float64))
+        assert np.isneginf(logp0[0]) and acc[0, np.isneginf(logp0)].all() and not acc[:, 6].any(), name
+        out[name + "_cfg"] = np.array([nup, ndn, dim, B, steps], dtype=np.int64)
+        out[name + "_g0"], out[name + "_g"], out[name + "_u"] = x0, gs, us
+        out[name + "_logp0"] = logp0
+        out[name + "_accept"] = np.packbits(acc.astype(np.uint8), axis=None)
+        out[name + "_x"], out[name + "_logp"] = x, logp
+        print("edges", name, "acc-rate", acc.mean(), "logp0", np.array2string(logp0[:7], precision=1))
+    for k, v in out.items():
+        if k.endswith("_logp") and k.startswith("p"):
+            print("edges", k, np.array2string(v, precision=1))
+    np.savez_compressed(os.path.join(HERE, "g8_sampler_edges.npz"), **out)
+
+
+GROUPS = dict(mcmc=g_mcmc, slater=g_slater, backflow=g_backflow, cnf=g_cnf, gsvmc=g_gsvmc, betavmc=g_betavmc, d3=g_3d, edges=g_edges)
 
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GROUPS)

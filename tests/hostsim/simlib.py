@@ -89,12 +89,12 @@ def _tabs(nup, ndn, tab_up, tab_dn):
     return tu, td
 
 
-def logprob(x, nup, ndn, tab_up=None, tab_dn=None, wstate=None):
+def logprob(x, nup, ndn, tab_up=None, tab_dn=None, wstate=None, derivs=True):
     x = _d(x); B = x.shape[0]
     tu, td = _tabs(nup, ndn, tab_up, tab_dn); ws = _i(wstate) if wstate is not None else None
-    lp = np.empty(B); g = np.empty_like(x); l = np.empty(B)
+    lp = np.empty(B); g = np.empty_like(x) if derivs else None; l = np.empty(B) if derivs else None
     _ck(lib().ff_logprob(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), _p(ws), _p(x), _p(lp), _p(g), _p(l)))
-    return lp, g, l
+    return (lp, g, l) if derivs else lp
 
 
 def slater(x, orb, wstate=None, gout=None):

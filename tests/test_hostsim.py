@@ -1059,3 +1059,89 @@ def test_off_table_fallback_grids_loop(golden, nup, ndn):
     a_z, a_d = rng.randn(*z.shape) / B, rng.randn(B) / B
     gxt, gpt, _ = S.cnf_adjoint(z, a_z, a_d, tab); gxe, gpe, _ = S.cnf_adjoint(z, a_z, a_d, exact)
     np.testing.assert_array_equal(gxt, gxe); np.testing.assert_array_equal(gpt, gpe)
+
+
+# ---- singular and far-tail walkers (tests/golden/g8_sampler_edges.npz; the GPU versions: test_gpu_sampler_edges.py) ----------
+@pytest.fixture(scope="module")
+def g8():
+    from tests.common import sampler_edges
+    return sampler_edges()
+
+
+def test_edge_probes(g8):
+    """log p (ff_logprob, ff_slater_logabsdet_fwd, ff_logprob3d) at walkers on the origin or an axis (exactly -inf) and in the
+    far tail (to 1e-12), against the reference."""
+    from tests.common import EDGE_SHAPES, EDGE_SHAPES3D, assert_edge_logp
+    for nup, ndn in EDGE_SHAPES:
+        x, ref = g8[f"p{nup}_{ndn}_x"], g8[f"p{nup}_{ndn}_logp"]
+        assert_edge_logp(S.logprob(x, nup, ndn, derivs=False), ref)
+        if ndn == 0:
+            assert_edge_logp(2 * S.slater(x, np.arange(nup))[0], ref)
+    for nup, ndn in EDGE_SHAPES3D:
+        assert_edge_logp(S.logprob3d(g8[f"p3d{nup}_{ndn}_x"], nup, ndn)[0], g8[f"p3d{nup}_{ndn}_logp"])
+
+
+@pytest.mark.parametrize("name", ["c3_3", "c6_0", "c2_1", "c3d4_3"])
+def test_edge_chains(g8, name):
+    """The reference's crafted chains (origin, axis, far-tail, NaN and ordinary starts) through the noise-fed kernels:
+    accept masks and walkers bit for bit, log p to 1e-12."""
+    from tests.common import edge_chain, assert_edge_logp, bits_equal
+    nup, ndn, g0, g, u, accept, x_ref, lp_ref, _ = edge_chain(g8, name)
+    x, lp, acc = (S.mcmc_noise3d if g0.shape[-1] == 3 else S.mcmc_noise)(g0, g, u, nup, ndn)
+    assert (acc == accept).all() and bits_equal(x, x_ref)
+    assert_edge_logp(lp, lp_ref)
+
+
+@pytest.mark.parametrize("nup,ndn", [(3, 3), (6, 0), (2, 1), (10, 0)])
+def test_edge_coincident_and_philox(nup, ndn):
+    """Identical rows: log p = -inf as the oracle (the reference's value is LAPACK rounding noise); pairs kept together never
+    accept, separated ones accept step 1.  Then the Philox chain from every special start (ff_mcmc_continue) equals the
+    noise-fed chain on the materialised stream: walkers, log p and accept counts."""
+    from tests.common import coincident_chains, special_starts, bits_equal
+    g0, g, u, kept, sep = coincident_chains(nup, ndn, 12, 6)
+    assert np.isneginf(S.logprob(g0[:5], nup, ndn, derivs=False)).all()
+    x, lp, acc = S.mcmc_noise(g0, g, u, nup, ndn)
+    xo, lpo, acco = O.mcmc_noise(g0, g, u, nup, ndn)
+    assert (acc == acco).all() and bits_equal(x, xo) and np.allclose(lp, lpo, rtol=1e-12, atol=0, equal_nan=True)
+    assert not acc[:, kept].any() and np.isneginf(lp[kept]).all() and acc[0, sep].all()
+    B, steps = 20, 8
+    x0, _ = special_starts(nup, ndn, B, list(range(9)), seed=nup)
+    _, h, hu = S.rng_fill(B, nup + ndn, steps, 5, offset=2)
+    x1, lp1, acc1 = S.mcmc_noise(x0, h, hu, nup, ndn)
+    x2, lp2, cnt = S.mcmc_continue(x0, nup, ndn, steps, 5, offset=2)
+    assert bits_equal(x1, x2) and bits_equal(lp1, lp2) and (acc1.sum(0) == cnt).all()
+    assert acc1[0, 0] and not acc1[:, 6].any() and np.isnan(lp1[6]) and bits_equal(x1[6], x0[6])
+
+
+@pytest.mark.parametrize("nup,ndn", [(3, 3), (6, 0), (4, 3), (10, 0)])
+def test_edge_walkers_leave_others_alone(nup, ndn):
+    """Special walkers at the seams of the workgroups (lanes of one walker, DPP rows, LDS rows of the sixteen-lane kernel)
+    change no other walker: bit-identical to the same launch with ordinary walkers in their place, both feeds."""
+    from tests.common import special_starts, bits_equal
+    B, steps = 259, 4
+    pos = [0, 1, 2, 3, 31, 32, 63, 64, 127, 128, 129, B - 2, B - 1]
+    x0, plain = special_starts(nup, ndn, B, pos, seed=1)
+    rng = np.random.default_rng(2)
+    g = rng.standard_normal((steps, B, nup + ndn, 2)); u = rng.random((steps, B))
+    keep = np.setdiff1d(np.arange(B), pos)
+    for run in (lambda x: S.mcmc_noise(x, g, u, nup, ndn), lambda x: S.mcmc_continue(x, nup, ndn, steps, 9)):
+        xa, lpa, aa = run(x0)
+        xb, lpb, ab = run(plain)
+        assert bits_equal(xa[keep], xb[keep]) and bits_equal(lpa[keep], lpb[keep]) and (aa[..., keep] == ab[..., keep]).all()
+
+
+def test_edge_walker_state_orbital_sets():
+    """Several orbital sets per batch (BetaVMC): the origin and the axes zero more columns of the higher orbitals, and a NaN in a
+    coordinate that a walker's orbitals do not depend on must still make its row NaN (the Gaussian carries it): pair kernel,
+    both feeds, against the oracle."""
+    from tests.common import special_starts, bits_equal
+    sets = np.array([[0, 1, 2], [0, 1, 3], [0, 2, 5], [1, 3, 4], [3, 4, 5], [0, 4, 9]], dtype=np.int32)
+    B, steps = 48, 10
+    x0, _ = special_starts(3, 0, B, list(range(24)), seed=3)
+    ws = np.sort(np.random.default_rng(4).integers(0, len(sets), size=B)).astype(np.int32)
+    assert ws[6] == 1          # the NaN walker (x coordinate) has orbitals (0,0), (0,1), (0,2): none depends on x
+    _, g, u = S.rng_fill(B, 3, steps, 5)
+    x1, lp1, acc1 = S.mcmc_noise(x0, g, u, 3, 0, tab_up=sets, wstate=ws)
+    xo, lpo, acco = O.mcmc_noise(x0, g, u, 3, 0, tab_up=sets, wstate=ws)
+    assert (acc1 == acco).all() and bits_equal(x1, xo) and np.allclose(lp1, lpo, rtol=1e-12, atol=0, equal_nan=True)
+    assert np.isnan(lp1[6]) and not acc1[:, 6].any()

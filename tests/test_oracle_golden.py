@@ -279,3 +279,50 @@ def test_3d_local_energy_and_gradient_vs_reference(golden, name):
     _, gp, _ = O.cnf_adjoint(z, dl, w[:, None, None] * g0, -w, net, rtol=1e-10, atol=1e-12)
     ref = gsvmc_param_grads(G, name)
     np.testing.assert_allclose(gp, ref, atol=1e-8 * np.abs(ref).max())
+
+
+# ---- g8: singular and far-tail walkers (tests/golden/make_golden.py edges) --------------------------------------------------
+@pytest.fixture(scope="module")
+def g8():
+    from tests.common import sampler_edges
+    return sampler_edges()
+
+
+def test_edge_logprob_probes(g8):
+    """log p at every particle on the origin or on an axis (a zero column of the Slater matrix: exactly -inf, as LAPACK's
+    zero pivot) and on rings of radius 8..30 (log p down to -10^4), against the reference."""
+    from tests.common import EDGE_SHAPES, EDGE_SHAPES3D, assert_edge_logp
+    for nup, ndn in EDGE_SHAPES:
+        tag = f"p{nup}_{ndn}"
+        assert_edge_logp(O.logprob(g8[tag + "_x"], nup, ndn, derivs=False), g8[tag + "_logp"])
+    for nup, ndn in EDGE_SHAPES3D:
+        tag = f"p3d{nup}_{ndn}"
+        assert_edge_logp(O.logprob3d(g8[tag + "_x"], nup, ndn, derivs=False), g8[tag + "_logp"])
+
+
+@pytest.mark.parametrize("name", ["c3_3", "c6_0", "c2_1", "c3d4_3"])
+def test_edge_chains(g8, name):
+    """Chains from the origin, the axes, rings at r = 16..30, a NaN walker and ordinary walkers with the reference's crafted
+    noise: accept masks and walkers bit for bit, log p to 1e-12 (a -inf start accepts its first proposal; the NaN walker never
+    moves and keeps log p = NaN)."""
+    from tests.common import edge_chain, assert_edge_logp, bits_equal
+    nup, ndn, g0, g, u, accept, x_ref, lp_ref, lp0_ref = edge_chain(g8, name)
+    run = O.mcmc_noise3d if g0.shape[-1] == 3 else O.mcmc_noise
+    x, lp, acc = run(g0, g, u, nup, ndn)
+    assert (acc == accept).all()
+    assert bits_equal(x, x_ref)
+    assert_edge_logp(lp, lp_ref)
+    assert np.isneginf(lp0_ref[0]) and acc[0, 0] == 1 and not acc[:, 6].any() and np.isnan(lp[6])
+
+
+@pytest.mark.parametrize("nup,ndn", [(3, 3), (6, 0), (2, 1), (4, 3)])
+def test_edge_coincident_particles(nup, ndn):
+    """Identical rows (a coincident same-spin pair or triple): log p = -inf as in exact arithmetic; a chain whose noise keeps
+    the particles together never accepts, one whose first proposal separates them accepts step 1.  The reference returns a
+    finite value here that depends on LAPACK's rounding: a deliberate deviation, not a tolerance."""
+    from tests.common import coincident_chains
+    g0, g, u, kept, sep = coincident_chains(nup, ndn, 12, 6)
+    assert np.isneginf(O.logprob(g0[:5], nup, ndn, derivs=False)).all()
+    x, lp, acc = O.mcmc_noise(g0, g, u, nup, ndn)
+    assert not acc[:, kept].any() and np.isneginf(lp[kept]).all() and (x[kept] == g0[kept]).all()
+    assert acc[0, sep].all() and np.isfinite(lp[sep]).all()
