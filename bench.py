@@ -16,16 +16,21 @@ estimator all-reduces of fermiflow_amd/dist.py).  value = n_gpus * walkers * 100
 (parity-test cases; their lines are kept under profiles/, the driver's line is the default workload).
   --scaling strong  the global batch stays at --walkers-per-gpu (default 65 536) however many GPUs share it
                     (BASELINE.json words its metric "65536 walkers, 1/2/4/8 GPUs"); default: weak, that many walkers PER GPU.
-A second, shorter timed leg (`trained_leg`) repeats the measurement after --trained-iters untimed training iterations at
-lr 1e-4: as the flow strengthens the ODE solves take more steps (tools/probes/long_run.py), so the headline -- synthetic
-weights held in place by a tiny learning rate -- is the best case; both numbers are on the line.
 
-Extra objects on the JSON line (rank 0, N = 1): `roofline` for the dominant kernel (the fused local-energy
-integration) with its live HIP-event time, its algorithmic flops and -- from four rocprofv3 --pmc child
-passes of this very script -- its HBM traffic, VALU-active / waiting shares of the wave-cycles, LDS bank-conflict share and
-matrix-core operation count; `roofline_adjoint`, `roofline_mcmc` for the other two kernels above
-10 % of a step; `roofline_hbm` (parity-mode Metropolis sweep: the HBM-bound kernel of the path), `roofline_pairwise`
-(stand-alone potential / backflow kernels); `stages_ms`; `cpu_baseline` (the C oracle on the host cores, bounded sample).
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked, and prints the JSON line: the headline,
+E / E_std of the last timed step, and `roofline` for the dominant kernel (the fused local-energy integration) with the
+HIP-event time and RHS-evaluation count the timed steps themselves recorded and its algorithmic flops.
+
+--full adds everything else the benchmark measures or checks, each in runs of its own after the timed steps:
+`stages_ms` (a second loop of K steps with stage markers); a second, shorter timed leg (`trained_leg`) after --trained-iters
+untimed training iterations at lr 1e-4 -- as the flow strengthens the ODE solves take more steps (tools/probes/long_run.py), so
+the headline, synthetic weights held in place by a tiny learning rate, is the best case; `long_window_leg` (K < 200),
+`reference_semantics_leg`, `policy_error`, `driver_leg`; `comm` (N > 1); and (rank 0, N = 1) the roofline's HBM traffic,
+VALU-active / waiting shares of the wave-cycles, LDS bank-conflict share and matrix-core operation count from rocprofv3 --pmc
+child passes of this very script; `roofline_adjoint`, `roofline_mcmc` for the other two kernels above 10 % of a step;
+`roofline_hbm` (parity-mode Metropolis sweep: the HBM-bound kernel of the path), `roofline_pairwise` (stand-alone potential /
+backflow kernels); `cpu_baseline` (the C oracle on the host cores, bounded sample).  --full --no-extras keeps only `stages_ms`
+(and `comm`).
 """
 import argparse
 import json
@@ -105,9 +110,9 @@ PMC_PASSES = (("FETCH_SIZE",), ("WRITE_SIZE",),
               ("SQ_INSTS_VALU_MFMA_MOPS_F32", "SQ_INSTS_MFMA", "SQ_BUSY_CYCLES"))
 
 
-def pmc_counters(kernel_substr, argv, passes=PMC_PASSES, child_args=("--steps", "2", "--warmup", "1", "--no-extras")):
+def pmc_counters(kernel_substr, argv, passes=PMC_PASSES, child_args=("--steps", "2", "--warmup", "1")):
     """Per-launch averages of hardware counters of one kernel, from `rocprofv3 --pmc` child passes of this script (counters
-    in their own runs, no tracing; --steps 2 --no-extras).  Returns (dict counter -> value per launch, None) or (None, reason).
+    in their own runs, no tracing; a plain run of --steps 2).  Returns (dict counter -> value per launch, None) or (None, reason).
     kernel_substr may be a tuple: the counters of all those kernels are added up and divided by the launches of the FIRST one
     (a pass that runs as several kernels side by side: the routed local-energy pass)."""
     names = (kernel_substr,) if isinstance(kernel_substr, str) else tuple(kernel_substr)
@@ -184,7 +189,7 @@ def main():
     # defaults: the GPU reaches its steady clocks only after some ten iterations (tools/probes/warmup_sweep.sh: 1.93 ms per iteration
     # at --steps 5 --warmup 2, 1.89 at 10/2, 1.84 at 20/2, 1.81 at 20/5 and 20/10: every stage shrinks by the same factor)
     # (a 20-step window is 31 ms, two scheduler hiccups wide -- a bare run now times 200 steps; when the caller asks
-    # for fewer, a `long_window_leg` of 200 steps rides on the same line)
+    # for fewer, --full adds a `long_window_leg` of 200 steps to the same line)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", choices=["gsvmc", "beta", "n12", "c5"], default="gsvmc")
@@ -195,16 +200,20 @@ def main():
                     help="precision of the sensitivity matrices J, A, S in the matrix-core local-energy kernel (11 particles and more): "
                          "64, or 32 = the fp32 MFMA path BASELINE.json configs[4] names; default: 32 for --workload c5, 64 otherwise")
     ap.add_argument("--trained-iters", type=int, default=300,
-                    help="untimed training iterations at lr 1e-4 in front of the second timed leg (0 = no second leg)")
+                    help="(--full) untimed training iterations at lr 1e-4 in front of the second timed leg (0 = no second leg)")
     ap.add_argument("--nup", type=int, default=0)
     ap.add_argument("--ndown", type=int, default=-1)
     ap.add_argument("--Z", type=float, default=2.0)
     ap.add_argument("--lr", type=float, default=2e-5,
                     help="Adam step; small so the synthetic weights (hence the ODE step counts) stay put over the run "
                          "(the reference's 1e-2 from these weights changes eta by 250 %% per step; --lr 1e-2 runs it)")
-    ap.add_argument("--cpu-walkers", type=int, default=4096, help="sample size of the CPU baseline (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stand-alone kernel legs, the PMC passes and the CPU baseline")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline.traffic = null)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run everything else the benchmark measures or checks (stage times, the other legs, "
+                         "stand-alone kernels, PMC passes, CPU baseline); without it a run does only what the headline needs")
+    ap.add_argument("--cpu-walkers", type=int, default=4096, help="(--full) sample size of the CPU baseline (0 = skip)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="(--full) skip the legs, the stand-alone kernels, the PMC passes and the CPU baseline: stage times only")
+    ap.add_argument("--no-pmc", action="store_true", help="(--full) skip the rocprofv3 --pmc child passes (roofline.traffic = null)")
     ap.add_argument("--standalone-leg", action="store_true",
                     help="(child passes) run only the stand-alone HBM-bound kernels -- parity-mode Metropolis sweep, potential -- three times and exit")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -213,6 +222,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Launched bare (`python bench.py --gpus N`): this parent starts the N ranks itself -- before anything here has
@@ -309,8 +319,8 @@ def main():
         step()
     # The timed region carries ONE event pair per step (around the local-energy pass: roofline.avg_launch_ms is measured live, on the
     # launch stream, inside the region the headline is measured in).  The five stage markers stay out of it: each is a hipEventRecord
-    # -- about 8 us of pipeline bubble on this GPU, 3 % of an iteration together (tools/probes/host_ahead.py) -- and stages_ms comes
-    # from a second loop of the same length right behind the timed one.
+    # -- about 8 us of pipeline bubble on this GPU, 3 % of an iteration together (tools/probes/host_ahead.py) -- and stages_ms (--full)
+    # comes from a second loop of the same length right behind the timed one.
     model.profile = {"stages": False}
     fence()
     t0 = time.perf_counter()
@@ -326,30 +336,33 @@ def main():
         dump_outputs(args.dump_outputs, model, wl, last_loss[0])
     prof, model.profile = model.profile, None
     E_head, Estd_head = model.E, model.E_std
-    _v = gs.cnf.v_wrapper.v      # the headline's weights, for the CPU baseline (the later legs train them on)
-    w_head = (tuple(t.detach().cpu().numpy().copy() for t in (_v.eta.fc1.weight, _v.eta.fc1.bias, _v.eta.fc2.weight)),
-              tuple(t.detach().cpu().numpy().copy() for t in (_v.mu.fc1.weight, _v.mu.fc1.bias, _v.mu.fc2.weight)))
+    w_head = None
+    if extras:
+        _v = gs.cnf.v_wrapper.v      # the headline's weights, for the CPU baseline (the later legs train them on)
+        w_head = (tuple(t.detach().cpu().numpy().copy() for t in (_v.eta.fc1.weight, _v.eta.fc1.bias, _v.eta.fc2.weight)),
+                  tuple(t.detach().cpu().numpy().copy() for t in (_v.mu.fc1.weight, _v.mu.fc1.bias, _v.mu.fc2.weight)))
     beta_head = (model.F, model.F_std, model.S) if wl == "beta" else None
     same = None
-    if rank == 0 and n_gpus == 1 and not args.no_extras and args.cpu_walkers > 0 and wl in ("gsvmc", "n12"):
+    if rank == 0 and n_gpus == 1 and extras and args.cpu_walkers > 0 and wl in ("gsvmc", "n12"):
         # One untimed sweep on EXACTLY these weights (no Adam step behind it): its first walkers and their local energies are what the
         # CPU baseline's oracle is given further down, so that E / E_std of both are estimates over the same sample
         with torch.no_grad():
             model(B_glob)
         ns = args.cpu_walkers if wl == "gsvmc" else max(256, args.cpu_walkers // 8)
         same = (model.x[:ns].cpu().numpy().copy(), model.Eloc[:ns].cpu().numpy().copy())
-    model.profile = {}
-    fence()
-    t0s = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    fence()
-    dt_marked = time.perf_counter() - t0s
-    prof_stages, model.profile = model.profile, None
+    if args.full:
+        model.profile = {}
+        fence()
+        t0s = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        dt_marked = time.perf_counter() - t0s
+        prof_stages, model.profile = model.profile, None
 
     # ---- the same loop over >= 200 steps (only when the caller's K is shorter): the headline's window at K = 20 is 31 ms
     long_leg = None
-    if args.steps < 200 and wl != "c5" and not args.no_extras:
+    if args.steps < 200 and wl != "c5" and extras:
         kl = 200
         model.profile = {"stages": False}
         fence()
@@ -383,7 +396,7 @@ def main():
         return ((e_ - tight).abs() / tight.abs()).max().item()
 
     ref_leg = None
-    if wl == "gsvmc" and not args.no_extras:
+    if wl == "gsvmc" and extras:
         with torch.no_grad():
             zr = model.basedist.sample(model.orbitals_up, model.orbitals_down, (wpg,))
         err_policy = eloc_error(zr)
@@ -413,7 +426,7 @@ def main():
     # ---- configs[3] / configs[4]: the tolerance policy's largest E_loc error against a 1e-11 solve on this line too
     #      (fp64 sensitivity matrices for the reference solve whatever --sens-bits the sweep runs at), two fresh batches
     policy_err = None
-    if wl in ("n12", "c5") and not args.no_extras and world == 1:
+    if wl in ("n12", "c5") and extras and world == 1:
         nsub = min(wpg, 32768 if wl == "n12" else 16384)
         errs = []
         for sd in (31, 32):
@@ -435,7 +448,7 @@ def main():
     #      place by the tiny learning rate: its ODE step counts are the best case)
     trained = None
     n_tr = args.trained_iters if wl != "c5" else 0
-    if n_tr > 0 and not args.no_extras:
+    if n_tr > 0 and extras:
         for g in opt.param_groups:
             g["lr"] = 1e-4
         for _ in range(n_tr):
@@ -475,7 +488,7 @@ def main():
     # ---- driver leg (VERDICT r04 next #1a; SURVEY 8(d) weights (i)): what a user of the drop-in driver runs -- init_zeros() flow
     #      (src/FermionHO2D.py:40-43), Adam lr = 1e-2 (:61), the training loop of :66-72 for 300 iterations on this workload's walkers
     driver = None
-    if wl == "gsvmc" and not args.no_extras:
+    if wl == "gsvmc" and extras:
         dm = G._model(dev, nup, ndown, args.Z)
         dv = dm.cnf.v_wrapper.v
         dv.eta.init_zeros(); dv.mu.init_zeros()
@@ -517,14 +530,7 @@ def main():
                   "headline_policy_eloc_max_rel_err": max(errs), "headline_policy_eloc_max_rel_err_by_batch": errs, "bar": 1e-5}
         del dm, dopt
 
-    # ---- per-stage times and the dominant kernel's roofline (HIP events recorded on the launch stream)
-    names = ["mcmc", "generate", "eloc", "estimator", "adjoint"]
-    stages = {k: 0.0 for k in names}
-    for ev in prof_stages["events"]:
-        prev = ev["t0"]
-        for k in names:
-            stages[k] += prev.elapsed_time(ev[k]); prev = ev[k]
-    stages = {k: v / args.steps for k, v in stages.items()}
+    # ---- the dominant kernel's roofline (HIP events recorded on the launch stream by the timed steps)
     k_ms = sum(a.elapsed_time(b) for a, b in prof["pass1"]) / args.steps
     evals = sum(int(s[0].item()) for s in prof["eloc_stats"]) / args.steps          # RHS evaluations summed over walkers
     M, R, H = dim * n, n * (n - 1) // 2 + n, 50
@@ -580,10 +586,18 @@ def main():
                                   f"walker prefetch {'on' if getattr(model, 'prefetch_walkers', False) else 'off'}), "
                                   f"{wpg} walkers/GPU, 100 Metropolis steps/iter, seeded gaussian weights x(30,300), Adam lr={args.lr}",
                       "global_walkers": B_glob, "parallelism": f"walker-dp{n_gpus}"},
-           "E": E_head, "E_std": Estd_head, "stages_ms": stages,
-           "stages_note": "stage markers (hipEventRecord, ~8 us of pipeline bubble each) are not in the timed region: stages_ms is a second loop "
-                          f"of {args.steps} steps right behind it, which ran at {dt_marked / args.steps * 1e3:.4f} ms per step with its markers",
-           "roofline": roofline}
+           "E": E_head, "E_std": Estd_head, "roofline": roofline}
+    if args.full:
+        # ---- per-stage times (HIP events of the stage-marker loop)
+        names = ["mcmc", "generate", "eloc", "estimator", "adjoint"]
+        stages = {k: 0.0 for k in names}
+        for ev in prof_stages["events"]:
+            prev = ev["t0"]
+            for k in names:
+                stages[k] += prev.elapsed_time(ev[k]); prev = ev[k]
+        out["stages_ms"] = {k: v / args.steps for k, v in stages.items()}
+        out["stages_note"] = ("stage markers (hipEventRecord, ~8 us of pipeline bubble each) are not in the timed region: stages_ms is a second loop "
+                              f"of {args.steps} steps right behind it, which ran at {dt_marked / args.steps * 1e3:.4f} ms per step with its markers")
     if long_leg is not None:
         out["long_window_leg"] = long_leg
         # the same loop over a 200-step window, next to `value` (the K-step headline is a ~30 ms window on weights that
@@ -608,7 +622,7 @@ def main():
         out["trained_leg"] = trained
     if driver is not None:
         out["driver_leg"] = driver
-    if world > 1:
+    if world > 1 and args.full:
         # ---- the communicator the N > 1 numbers were measured on: backend, ranks, devices, and the two all-reduces
         #      a sweep adds (four estimator sums; the 300-double gradient) timed alone, 100 repetitions each
         comm = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "collectives_per_iteration": 2,
@@ -640,7 +654,7 @@ def main():
     if wl == "beta":
         out.update(F=beta_head[0], F_std=beta_head[1], S=beta_head[2])
 
-    if rank == 0 and n_gpus == 1 and not args.no_extras:
+    if rank == 0 and n_gpus == 1 and extras:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
         def timed(fn, reps=5):

@@ -225,6 +225,24 @@ def test_four_ranks_strong_scaling_dry_run():
     assert abs(four["E_std"] - one["E_std"]) < 1e-10 * one["E_std"]
 
 
+def test_bench_plain_run_prints_the_headline_and_full_adds_the_rest():
+    """A plain bench.py run sets up, warms up, times its steps and prints the headline (with E / E_std and the roofline the timed
+    steps recorded); the other legs, stage times, stand-alone kernels, counter passes and CPU baseline run only under --full.  The
+    timed steps are the same either way: the same E and E_std."""
+    common = ["--steps", "3", "--warmup", "1", "--walkers-per-gpu", "4096"]
+    rc, plain, err = _bench(common)
+    assert rc == 0, err[-2000:]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "E", "E_std", "roofline"):
+        assert k in plain, k
+    assert plain["steps"] == 3 and plain["warmup"] == 1 and plain["value"] > 0 and plain["roofline"]["traffic"] is None
+    assert not {"stages_ms", "long_window_leg", "reference_semantics_leg", "trained_leg", "driver_leg", "roofline_adjoint",
+                "roofline_mcmc", "roofline_hbm", "roofline_pairwise", "cpu_baseline"} & set(plain)
+    rc, full, err = _bench(common + ["--full", "--no-extras"])
+    assert rc == 0, err[-2000:]
+    assert set(full["stages_ms"]) == {"mcmc", "generate", "eloc", "estimator", "adjoint"}
+    assert abs(full["E"] - plain["E"]) < 1e-12 * abs(plain["E"]) and abs(full["E_std"] - plain["E_std"]) < 1e-10 * plain["E_std"]
+
+
 def test_ff_comm_single_rank_all_reduce():
     """ff_comm_* (SURVEY 8(b)'s minimum symbol set; include/fermiflow.h): the RCCL wrappers a torch-free caller sums the estimator's
     buffers with.  One rank on the one GPU of the test box: id, init, an in-place all-reduce of the 4-double and the 300-double
