@@ -79,7 +79,7 @@ FF_D void ff_sigma_derivs(double s, double* out) {
 // hidden unit, joined by a quad reduction in a fixed order: the sequential chain of H sigmoid evaluations per lane was the kernel.
 #define FF_TAB_NODES_PER_WG 32
 #ifndef FF_TAB_GRID
-#define FF_TAB_GRID 256                     // one workgroup per CU: 2 x 2049 nodes (h = 1/64) in one round, 2 x 16385 in four
+#define FF_TAB_GRID 256                     // one workgroup per CU: 2 x 2049 nodes (h = 1/64) in one round, 2 x 16385 in five
 #endif
 __global__ void __launch_bounds__(128) ff_table_kernel(ff_net net, double* __restrict__ tab) {
   FF_SETPRIO();

@@ -1,5 +1,6 @@
 """Helpers shared by the oracle, hostsim and GPU parity tests."""
 import hashlib
+import math
 import os
 
 import numpy as np
@@ -143,6 +144,70 @@ def T(a, dev, dtype=torch.float64):
 
 def N(t):
     return t.detach().cpu().numpy()
+
+
+# ---- stiff weight sets: every regime of the radial table's header (fermiflow_amd/csrc/ff_radial.h)
+def stiff_net(target, seed=1, H=50, amp=0.05, stiff="eta"):
+    """Seeded (eta, mu) weights (w1, b1, w2) with max|w1| over both nets exactly `target`, carried by the `stiff` net (the other
+    one's |w1| stays at or below target / 2).  The sigmoid centres c = -b1 / w1 are spread over 0.3 .. 9 (across r = 8, where the
+    adjoint's deposit table leaves LDS), so that the sharp switches sit at radii the walkers take; w2 ~ amp / max(target, 2) keeps
+    the flow's first derivative bounded while the higher ones grow with the target."""
+    rng = np.random.RandomState(seed)
+
+    def one(wmax, a):
+        w1 = rng.uniform(0.25, 1.0, H) * wmax * rng.choice([-1.0, 1.0], H)
+        w1[rng.randint(H)] = wmax * (1.0 if rng.rand() < 0.5 else -1.0)
+        c = rng.uniform(0.3, 9.0, H)
+        return w1, -w1 * c, rng.standard_normal(H) * a / max(float(target), 2.0)
+    # (mu multiplies x_i itself, a growth rate summed over H units: at eta's amplitude it carries walkers off the table)
+    if stiff == "eta":
+        return one(float(target), amp), one(0.5 * float(target), 0.2 * amp)
+    return one(0.5 * float(target), amp), one(float(target), 0.2 * amp)
+
+
+def radial_header(w):
+    """Slots 0..5 of the radial table's header for max|w1| = w: the rule of ff_radial.h restated.
+    (1/h, h, nodes, table refused, deposit grid refused, coefficients per deposit row)"""
+    lg = 6
+    while lg < 9 and w * 2.0 ** -lg > 0.06:
+        lg += 1
+    bad = not (w * 2.0 ** -lg <= 0.06)
+    xd = 1.5 * w / 16.0
+    nrow = next((n for n in (6, 8, 10) if xd ** n / math.factorial(n) <= 4.5e-12), 12)
+    return [2.0 ** lg, 2.0 ** -lg, float(32 * 2 ** lg + 1), float(bad), 0.0 if w / 16.0 <= 0.4 else 1.0, float(nrow)]
+
+
+FF_TAB_HDR, FF_TAB_ROW, FF_TAB_NMAX = 16, 10, 32 * 512 + 1       # ff_radial.h: the table tensor's layout
+
+# the regimes of tests/test_gpu_stiff_weights.py: name -> (max|w1|, the net that carries it)
+STIFF_REGIMES = {"w0.4": (0.4, "eta"), "w1": (1.0, "eta"), "w2.5": (2.5, "eta"), "w3.7": (3.7, "eta"), "w5": (5.0, "eta"),
+                 "w5mu": (5.0, "mu"), "w7": (7.0, "eta"), "w12": (12.0, "eta"), "w25": (25.0, "eta"), "w40": (40.0, "eta")}
+STIFF_NARROW_REGIMES = ["w0.4", "w1", "w2.5", "w3.7", "w5", "w7", "w12", "w25", "w40"]       # every regime of the table
+STIFF_BROAD_REGIMES = ["w3.7", "w5", "w7", "w25", "w40"]       # 12 rows, h = 1/128, deposit refused, h = 1/512, table refused
+
+
+def radial_nodes_ref(w, h, nodes):
+    """f^(0..8)(j h), j < nodes, of one scalar MLP f(r) = sum w2 sigma(w1 r + b1) in long double: (nodes, 9).  The derivatives of
+    sigma come from the recursion P_{n+1}(s) = P_n'(s) s (1 - s) on polynomials in s = sigma, built here independently of the
+    kernels' coefficient table."""
+    P = [np.polynomial.Polynomial([0.0, 1.0])]
+    s1 = np.polynomial.Polynomial([0.0, 1.0, -1.0])
+    for _ in range(8):
+        P.append(P[-1].deriv() * s1)
+    w1, b1, w2 = (np.asarray(a, dtype=np.longdouble) for a in w)
+    r = np.arange(nodes, dtype=np.longdouble) * np.longdouble(h)
+    out = np.zeros((nodes, 9), dtype=np.longdouble)
+    for k in range(len(w1)):
+        s = 1 / (1 + np.exp(-(w1[k] * r + b1[k])))
+        wp = w2[k]
+        for n in range(9):
+            c = P[n].coef.astype(np.longdouble)
+            v = np.zeros_like(s)
+            for ck in c[::-1]:
+                v = v * s + ck
+            out[:, n] += wp * v
+            wp = wp * w1[k]
+    return out
 
 
 def make_mlp(w, dev):

@@ -330,3 +330,25 @@ def test_compact_finish_workspace_sizes():
     # configs[4]: 131 072 walkers of 20 particles in d = 3 -- 4.09 GB of J^T alone in the full layout, 64 MB compact
     assert full(131072, 20, 3) > 4.0e9 and nd(131072, 20, 3, 1) == 8 * (131072 * 61 + 2) < 64.1e6
     assert native.COMPACT_WORKSPACE_BYTES == 32 << 30 and full(1 << 20, 20, 3) > native.COMPACT_WORKSPACE_BYTES > full(1 << 19, 20, 3)
+
+
+def test_stiff_regimes_cover_every_grid_row_length_and_refusal():
+    """The weight regimes of tests/test_gpu_stiff_weights.py, through the header rule of ff_radial.h restated (tests/common.py
+    radial_header): the narrow shapes meet every grid spacing, every deposit row length and both refusals; the wide and 3-D shapes the
+    12-row, h = 1/128, deposit-refused, h = 1/512 and table-refused regimes.  A threshold change in the restatement that shrank this
+    matrix fails here; the GPU node test asserts the device's header equals the restatement."""
+    from tests.common import STIFF_BROAD_REGIMES, STIFF_NARROW_REGIMES, STIFF_REGIMES, radial_header, stiff_net
+    hdr = {r: radial_header(STIFF_REGIMES[r][0]) for r in STIFF_REGIMES}
+    usable = [hdr[r] for r in STIFF_NARROW_REGIMES if not hdr[r][3]]
+    assert {h[0] for h in usable} == {64.0, 128.0, 256.0, 512.0}
+    assert {h[5] for h in usable if not h[4]} == {6.0, 8.0, 10.0, 12.0}
+    assert any(hdr[r][3] for r in STIFF_NARROW_REGIMES) and any(hdr[r][4] and not hdr[r][3] for r in STIFF_NARROW_REGIMES)
+    broad = [hdr[r] for r in STIFF_BROAD_REGIMES]
+    assert any(h[5] == 12 and h[0] == 64 and not h[4] for h in broad) and any(h[0] == 128 and not h[4] for h in broad)
+    assert any(h[0] == 512 and not h[3] for h in broad)
+    assert any(h[3] for h in broad) and any(h[4] and not h[3] for h in broad)
+    assert STIFF_REGIMES["w5mu"][1] == "mu"
+    for r, (target, stiff) in STIFF_REGIMES.items():        # the generator hits the target exactly, in the net it names
+        eta, mu = stiff_net(target, stiff=stiff)
+        top = eta if stiff == "eta" else mu
+        assert np.abs(top[0]).max() == target and max(np.abs(eta[0]).max(), np.abs(mu[0]).max()) == target, r

@@ -1145,3 +1145,51 @@ def test_edge_walker_state_orbital_sets():
     xo, lpo, acco = O.mcmc_noise(x0, g, u, 3, 0, tab_up=sets, wstate=ws)
     assert (acc1 == acco).all() and bits_equal(x1, xo) and np.allclose(lp1, lpo, rtol=1e-12, atol=0, equal_nan=True)
     assert np.isnan(lp1[6]) and not acc1[:, 6].any()
+
+
+@pytest.mark.parametrize("nup,ndn,target", [(4, 3, 2.5), (4, 3, 3.7), (4, 3, 5.0), (7, 6, 3.7), (7, 6, 5.0)])
+def test_stiff_tabulated_adjoint_beyond_three_plus_three(nup, ndn, target):
+    """The tabulated adjoints at 10- and 12-coefficient deposit rows and on the h = 1/128 table (tests/common.py stiff_net): the
+    one-radius-per-lane narrow kernel (4+3) and the one-walker-per-workgroup kernel (7+6) against the direct kernel of the exact net.
+    A row cut short moves gp by far more than the bar."""
+    from tests.common import radial_header, stiff_net
+    n = nup + ndn
+    eta, mu = stiff_net(target, H=16)
+    tab = S.Net(eta, mu, table=True)
+    hdr = radial_header(target)
+    assert list(tab.tab[:6]) == hdr and not hdr[3] and not hdr[4]
+    rng = np.random.default_rng(n)
+    B = 3 if n < 10 else 1
+    z = rng.normal(size=(B, n, 2))
+    az, ad = rng.normal(size=z.shape), rng.normal(size=B)
+    tol = dict(rtol=1e-9, atol=1e-11)
+    gx_e, gp_e, st_e = S.cnf_adjoint(z, az, ad, S.Net(eta, mu), **tol)
+    gx_t, gp_t, st_t = S.cnf_adjoint(z, az, ad, tab, **tol)
+    assert st_e[3] == 0 and st_t[3] == 0
+    assert not np.array_equal(gp_t, gp_e)              # the tabulated kernel served
+    np.testing.assert_allclose(gx_t, gx_e, atol=1e-12 * max(1.0, np.abs(gx_e).max()))
+    np.testing.assert_allclose(gp_t, gp_e, atol=1e-12 * np.abs(gp_e).max())        # measured <= 8e-15; rows capped at 6: 1e-10 .. 6e-9
+
+
+def test_stiff_deposit_refused_energy_adjoint_one_particle():
+    """1+0 at max|w1| = 7 (deposit grid refused: the lean direct kernel serves the table net, in two passes over the 50 hidden units,
+    unit0 = 0 and 32): ff_cnf_adjoint_energy of the table net bit-identical to the exact net's (ff_ode_adj_kernel), and both equal to
+    the oracle's gradient of the seeds the kernel forms."""
+    from tests.common import stiff_net
+    eta, mu = stiff_net(7.0)
+    tab = S.Net(eta, mu, table=True)
+    assert tab.tab[4] == 1.0 and tab.tab[3] == 0.0 and len(eta[0]) > 32
+    rng = np.random.default_rng(1)
+    B = 5
+    z, g0 = rng.normal(size=(B, 1, 2)), rng.normal(size=(B, 1, 2))
+    e = 2.0 + rng.normal(size=B)
+    E, scale = float(e.mean()), 1.0 / B
+    gx_t, gp_t, st_t = S.cnf_adjoint_energy(z, g0, e, E, scale, tab, rtol=1e-9, atol=1e-11)
+    gx_e, gp_e, st_e = S.cnf_adjoint_energy(z, g0, e, E, scale, S.Net(eta, mu), rtol=1e-9, atol=1e-11)
+    assert st_t[3] == 0 and st_e[3] == 0
+    np.testing.assert_array_equal(gp_t, gp_e)
+    np.testing.assert_array_equal(gx_t, gx_e)
+    w = (e - E) * scale
+    gxo, gpo, _ = O.cnf_adjoint(z, np.zeros(B), w[:, None, None] * g0, -w, O.Net(eta, mu), rtol=1e-11, atol=1e-13)
+    np.testing.assert_allclose(gp_t, gpo, atol=1e-7 * np.abs(gpo).max())
+    np.testing.assert_allclose(gx_t, gxo, atol=1e-7 * max(1.0, np.abs(gxo).max()))
