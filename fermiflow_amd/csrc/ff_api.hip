@@ -1,6 +1,6 @@
 // ff_api.hip -- library-wide pieces of the C ABI (version, error string) and the host-side set-up code that the
 // reference keeps in Python: enumeration of the low-lying many-body states (src/orbitals.py:14-54).
-#include "ff_common.h"
+#include "ff_host.h"
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -10,6 +10,18 @@ static thread_local char g_ff_err[256] = "";
 void ff_set_error(const char* msg) {
   strncpy(g_ff_err, msg ? msg : "", sizeof(g_ff_err) - 1);
   g_ff_err[sizeof(g_ff_err) - 1] = 0;
+}
+
+// Asked once per process; 256 (MI355X) when there is no device to ask: the workspace-size queries run without one.
+int64_t ff_device_cus() {
+  static int64_t n = 0;
+  if (n == 0) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+    n = cus;
+  }
+  return n;
 }
 
 namespace {

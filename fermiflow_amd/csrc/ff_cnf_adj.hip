@@ -791,32 +791,13 @@ __global__ void __launch_bounds__(256) ff_zero_kernel(double* __restrict__ p, si
 }
 
 // =================================================================================================
-extern void ff_set_error(const char* msg);
-#define FF_CHECK(cond, code, msg) do { if (!(cond)) { ff_set_error(msg); return code; } } while (0)
-#define FF_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { ff_set_error(hipGetErrorString(e_)); return FF_ELAUNCH; } } while (0)
-
+#include "ff_host.h"
 #include <stdlib.h>
 
-static int adj_G(int n, int d) { int M = n * d; return M > 0 && M <= FF_WAVE ? (FF_WAVE / M > 16 ? 16 : FF_WAVE / M) : 0; }   // = ff_geom<N,D>::G
 // Persistent grid: one wave per SIMD.  Every walker takes the same few steps here, so a static split is balanced, and
 // each workgroup flushes a private deposit table (25 KB) at its end -- the fewer workgroups the less HBM traffic
 // (measured, 65536 walkers: 4096 workgroups 1.09 ms, 1024 workgroups 0.92 ms).
-static int64_t adj_default_blocks() {
-  static int64_t n = 0;
-  if (n == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    n = 4 * (int64_t)cus;
-  }
-  return n;
-}
-
-static unsigned adj_grid(int64_t B, int G) {
-  int64_t ngroups = (B + G - 1) / G;
-  const int64_t cap = adj_default_blocks();
-  return (unsigned)(ngroups < cap ? ngroups : cap);
-}
+static unsigned adj_grid(int64_t B, int G) { return ff_grid(B, G, 4 * ff_device_cus()); }
 
 // Direct-evaluation adjoint: a lane keeps the parameter integrands of MAXU of its hidden units in registers, so one launch
 // integrates the gradient of M*MAXU units (all of the reference's default width 50 at once); wider nets (--Deta/--Dmu up to
@@ -862,19 +843,15 @@ static size_t adj_table_doubles(int64_t B, int Gtab) {   // one private table pe
 // workspace = [direct rows | private tables + Wtot | off-table flag]
 static size_t adj_direct_doubles(int64_t B, int G, int He, int Hm) { return (size_t)adj_grid(B, G) * G * (size_t)(3 * He + 3 * Hm); }
 
-// the narrow kernels are instantiated for n = 1..12 in d = 2 and n = 2..4 in d = 3; everything else (and everything under
-// FF_WIDE=1) goes to the one-walker-per-wave kernels of ff_adj_wide.h
-static bool adj_is_wide(int n, int d) {
-  const bool narrow = (d == 2 && n >= 1 && n <= 12) || (d == 3 && n >= 2 && n <= 4);
-  return ff_wide_supported(n, d) && (!narrow || ff_wide_forced());
-}
+// the narrow kernels are instantiated for the shapes of ff_ode.h (n = 1..12 in d = 2, n = 2..4 in d = 3); everything else (and
+// everything under FF_WIDE=1) goes to the one-walker-per-wave kernels of ff_adj_wide.h
+static bool adj_is_wide(int n, int d) { return ff_wide_supported(n, d) && (!ff_narrow_shape(n, d) || ff_wide_forced()); }
 
 // doubles of the layout one kernel family uses (0: that family does not serve (n, d))
 static size_t adj_ws_doubles(bool wide, int64_t B, int n, int d, int He, int Hm) {
   if (wide) return ff_wide_supported(n, d) ? adj_direct_doubles(B, 1, He, Hm) + adj_table_doubles(B, 1) + 1 + (size_t)B : 0;   // (+ B: opening steps, ff_ode.walker_h_equal)
-  const bool narrow = (d == 2 && n >= 1 && n <= 12) || (d == 3 && n >= 2 && n <= 4);
-  const int G = adj_G(n, d);
-  return (narrow && G) ? adj_direct_doubles(B, G, He, Hm) + adj_table_doubles(B, adj_tab_G(n, d) * FF_ADJ_WPW) + 1 : 0;
+  const int G = ff_geom_G(n, d);
+  return (ff_narrow_shape(n, d) && G) ? adj_direct_doubles(B, G, He, Hm) + adj_table_doubles(B, adj_tab_G(n, d) * FF_ADJ_WPW) + 1 : 0;
 }
 
 // The larger of the two families' layouts: which family a call uses is decided when it runs (ff_set_kernel_family / FF_WIDE may
@@ -907,11 +884,7 @@ int ff_cnf_adjoint_energy(void* stream, int64_t B, int n, int d, const ff_net* n
 static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* z_t0,
                         const double* a_z, const double* a_d, const double* w_e, const double* w_mean, const int32_t* w_index,
                         double w_scale, double* grad_x, double* grad_params, void* workspace, int32_t* stats) {
-  FF_CHECK(B >= 0 && n > 0 && d > 0 && net && ode && grad_params, FF_EINVAL, "ff_cnf_adjoint: bad argument");
-  FF_CHECK(net->He > 0 && net->ew1 && net->eb1 && net->ew2 && (net->Hm == 0 || (net->mw1 && net->mb1 && net->mw2)), FF_EINVAL,
-           "ff_cnf_adjoint: bad net");
-  FF_CHECK(net->He <= FF_HMAX && net->Hm <= FF_HMAX, FF_EUNSUPPORTED, "ff_cnf_adjoint: hidden width > 256");
-  FF_CHECK(ode->rtol > 0 && ode->atol > 0, FF_EINVAL, "ff_cnf_adjoint: tolerances must be positive");
+  if (const int st = ff_check_flow("ff_cnf_adjoint", B >= 0 && n > 0 && d > 0 && grad_params, net, ode)) return st;
   const int P = 3 * net->He + 3 * net->Hm;
   if (B == 0) {
     if (hipMemsetAsync(grad_params, 0, sizeof(double) * P, (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
@@ -919,14 +892,11 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
   }
   FF_CHECK(z_t0 && a_z && workspace, FF_EINVAL, "ff_cnf_adjoint: null pointer");
   ff_adj_args a = {};
-  a.B = B; a.net = *net; a.ta = ode->t0; a.tb = ode->t1; a.rtol = ode->rtol; a.atol = ode->atol;
-  a.max_steps = ode->max_steps > 0 ? ode->max_steps : 10000;
-  a.wcost = ode->walker_cost; a.order = ode->walker_order;
-  a.h_init = ode->walker_h_init; a.h_scale = ode->walker_h_uniform ? -fabs(ode->walker_h_scale) : fabs(ode->walker_h_scale); a.h_out = ode->walker_h_out; a.h_equal = ode->walker_h_equal;
+  ff_fill_common(a, B, net, ode, true);
   a.z_in = z_t0; a.az_in = a_z; a.ad_in = a_d; a.w_e = w_e; a.w_mean = w_mean; a.w_index = w_index; a.w_scale = w_scale; a.gx_out = grad_x; a.rows = (double*)workspace; a.stats = stats;
   const bool wide = adj_is_wide(n, d);      // the family of THIS call, read once: layout, memset and launches below all follow it
   {
-    const int Gq = wide ? 1 : adj_G(n, d);
+    const int Gq = wide ? 1 : ff_geom_G(n, d);
     if (Gq == 0) { ff_set_error("ff_cnf_adjoint: n*d > 64"); return FF_EUNSUPPORTED; }
     a.trows = a.rows + adj_direct_doubles(B, Gq, net->He, net->Hm);
     a.off_table = a.trows + adj_table_doubles(B, wide ? 1 : adj_tab_G(n, d) * FF_ADJ_WPW);
@@ -944,7 +914,7 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
   if (wide && a.h_equal && a.h_init) {
     const int64_t nh = a.h_scale < 0.0 ? 1 : B;      // (walker_h_uniform: one entry)
     double* hs = a.off_table + 1;
-    FF_LAUNCH(ff_open_steps_kernel, (unsigned)((nh + 255) / 256), 256, stream, nh, a.h_init, fabs(a.h_scale), a.ta, a.tb, hs);
+    FF_LAUNCH(ff_open_steps_kernel, ff_grid(nh, 256), 256, stream, nh, a.h_init, fabs(a.h_scale), a.ta, a.tb, hs);
     a.h_init = hs; a.h_scale = a.h_scale < 0.0 ? -1.0 : 1.0; a.h_equal = 0;
   }
   if (wide) {
@@ -955,13 +925,13 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
                                                                   FF_LAUNCH((ff_wide_adj_kernel<D_, W_, Q_>), grid, FF_WAVE * W_, stream, a, n); G = 1; }
     FF_WA(2, 2, 1) FF_WA(2, 4, 1) FF_WA(2, 4, 2) FF_WA(3, 2, 1) FF_WA(3, 4, 1) FF_WA(3, 4, 2)
 #undef FF_WA
-  } else
-  // both variants are enqueued; on the device exactly one of them runs, chosen by the radial-table header
-  // (no table / weights too stiff for the deposit grid -> direct evaluation), so the host never has to look at it
+  } else {
+    // both variants are enqueued; on the device exactly one of them runs, chosen by the radial-table header
+    // (no table / weights too stiff for the deposit grid -> direct evaluation), so the host never has to look at it
 #define FF_ND(N_, D_) if (n == N_ && d == D_) { if (net->radial_table) FF_LAUNCH((ff_ode_adjtab_kernel<N_, D_, FF_ADJ_WPW>), adj_grid(a.B, ff_adjtab_geom<N_, D_>::G * FF_ADJ_WPW), FF_WAVE * FF_ADJ_WPW, stream, a); launch_adj<N_, D_>(stream, a); G = ff_geom<N_, D_>::G; }
-  FF_ND(6, 2) else FF_ND(3, 2) else FF_ND(12, 2) else FF_ND(2, 2) else FF_ND(4, 2) else FF_ND(5, 2) else FF_ND(8, 2) else FF_ND(10, 2)
-  else FF_ND(1, 2) else FF_ND(7, 2) else FF_ND(9, 2) else FF_ND(11, 2) else FF_ND(2, 3) else FF_ND(3, 3) else FF_ND(4, 3)
+    FF_NARROW_COLUMNS(FF_ND) FF_NARROW_ROWS_ONLY(FF_ND)
 #undef FF_ND
+  }
   if (G == 0) {
     ff_set_error("fused CNF kernels serve n <= 24 particles with n*d <= 60 in d = 2, 3");
     return FF_EUNSUPPORTED;

@@ -1329,11 +1329,9 @@ ff_eloc_contract_kernel(int64_t B, int nup, int ndn, double Zc, int use_ho, cons
 }
 
 // =================================================================================================
-extern void ff_set_error(const char* msg);
+#include "ff_host.h"
 extern int ff_slater_rows_launch(void* stream, int d, int64_t B, int nup, int ndn, const int* tab_up, const int* tab_dn, const int* wstate,
                                  const double* z0, double* Q);
-#define FF_CHECK(cond, code, msg) do { if (!(cond)) { ff_set_error(msg); return code; } } while (0)
-#define FF_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { ff_set_error(hipGetErrorString(e_)); return FF_ELAUNCH; } } while (0)
 
 #include <stdlib.h>
 #include <string.h>
@@ -1343,16 +1341,10 @@ static constexpr int64_t FF_GRID_CAP = 1 << 20;      // without a work queue: on
 
 // With a radial table: the table kernel, then the direct-evaluation kernel as its (normally idle) fallback -- it returns
 // in its first instructions unless the table kernel left this launch's id in the event slot.  Without: direct only.
-// persistent grid of the queue mode: one wave per SIMD
-static int64_t fwd_queue_blocks() {
-  static int64_t n = 0;
-  if (n == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    n = 4 * (int64_t)cus;
-  }
-  return n;
+// Grid of a launch that takes G walkers per workgroup: with a work queue a persistent grid of `wps` waves per SIMD (four SIMDs per
+// CU), without one a workgroup per walker group
+static unsigned fwd_grid(const ff_fwd_args& a, int G, int wps = 1) {
+  return ff_grid(a.B, G, a.queue ? wps * 4 * ff_device_cus() : FF_GRID_CAP);
 }
 
 // Routing of the local-energy pass by cost class.  A launch cannot end before its longest chain of steps has: a walker with a
@@ -1473,10 +1465,7 @@ static int launch_routed(void* stream, int n, int d, const ff_fwd_args& a, F lau
 
 template <int N, int D, int MODE>
 static int launch_fwd(void* stream, const ff_fwd_args& a) {
-  constexpr int G = ff_geom<N, D>::G;
-  int64_t ngroups = (a.B + G - 1) / G;
-  const int64_t cap = a.queue ? fwd_queue_blocks() : FF_GRID_CAP;   // without a queue: one workgroup per walker group
-  unsigned grid = (unsigned)(ngroups < cap ? ngroups : cap);
+  const unsigned grid = fwd_grid(a, ff_geom<N, D>::G);
   auto table = [&](void* st, const ff_fwd_args& aa) { FF_LAUNCH((ff_ode_fwd_kernel<N, D, MODE, true>), grid, FF_WAVE, st, aa); };
   int routed = FF_ROUTE_NONE;
   if constexpr (MODE == 2 && N <= 3) routed = launch_routed(stream, N, D, a, table, false);
@@ -1493,10 +1482,7 @@ static int launch_fwd(void* stream, const ff_fwd_args& a) {
 // n = 10 48 -> 9.3 ms, n = 12 95 -> 14.7 ms)
 template <int N, int D>
 static void launch_split(void* stream, const ff_fwd_args& a) {
-  constexpr int G = FF_WAVE / (2 * N * D);
-  int64_t ngroups = (a.B + G - 1) / G;
-  const int64_t cap = a.queue ? fwd_queue_blocks() : FF_GRID_CAP;
-  const unsigned grid = (unsigned)(ngroups < cap ? ngroups : cap);
+  const unsigned grid = fwd_grid(a, FF_WAVE / (2 * N * D));
   if (a.evt) FF_LAUNCH((ff_eloc_split_kernel<N, D, true>), grid, FF_WAVE, stream, a);
   FF_LAUNCH((ff_eloc_split_kernel<N, D, false>), grid, FF_WAVE, stream, a);
 }
@@ -1506,9 +1492,7 @@ static void launch_split(void* stream, const ff_fwd_args& a) {
 template <int N, int D, int SPLIT>
 static void launch_rows(void* stream, const ff_fwd_args& a) {
   constexpr int G = FF_WAVE / (N * D * SPLIT) > 16 ? 16 : FF_WAVE / (N * D * SPLIT);
-  int64_t ngroups = (a.B + G - 1) / G;
-  const int64_t cap = a.queue ? fwd_queue_blocks() : FF_GRID_CAP;
-  const unsigned grid = (unsigned)(ngroups < cap ? ngroups : cap);
+  const unsigned grid = fwd_grid(a, G);
   if (a.evt) FF_LAUNCH((ff_eloc_rows_kernel<N, D, SPLIT, true>), grid, FF_WAVE, stream, a);
   FF_LAUNCH((ff_eloc_rows_kernel<N, D, SPLIT, false>), grid, FF_WAVE, stream, a);
 }
@@ -1519,10 +1503,8 @@ static void launch_rows(void* stream, const ff_fwd_args& a) {
 // Matrix-core local-energy kernel (ff_eloc_mfma.h): four walkers per wave, M = n d <= 12, two waves per SIMD
 template <int N, int D>
 static int launch_mfma(void* stream, const ff_fwd_args& a) {
-  const int64_t ngroups = (a.B + 3) / 4;
-  const int64_t cap = a.queue ? FF_MFMA_WPS * fwd_queue_blocks() : FF_GRID_CAP;
   auto table = [&](void* st, const ff_fwd_args& aa) {
-    FF_LAUNCH((ff_eloc_mfma_kernel<N, D, true, FF_MFMA_WPS>), (unsigned)(ngroups < cap ? ngroups : cap), FF_WAVE, st, aa);
+    FF_LAUNCH((ff_eloc_mfma_kernel<N, D, true, FF_MFMA_WPS>), fwd_grid(a, 4, FF_MFMA_WPS), FF_WAVE, st, aa);
   };
   const int routed = launch_routed(stream, N, D, a, table, (a.fin.on & 1) && N % 2 == 0 && D == 2);
   if (routed == FF_ROUTE_FAILED) return FF_ELAUNCH;
@@ -1530,8 +1512,7 @@ static int launch_mfma(void* stream, const ff_fwd_args& a) {
   t_eloc_fb.fused = (a.fin.on & 1) && N % 2 == 0 && D == 2;      // (what the kernel's epilogue tests)
   t_eloc_fb.routed = routed == FF_ROUTE_DONE;
   t_eloc_fb.evt = a.evt; t_eloc_fb.evt_id = a.evt_id;
-  const int64_t cap1 = a.queue ? fwd_queue_blocks() : FF_GRID_CAP;
-  FF_LAUNCH((ff_eloc_mfma_kernel<N, D, false, 1>), (unsigned)(ngroups < cap1 ? ngroups : cap1), FF_WAVE, stream, a);
+  FF_LAUNCH((ff_eloc_mfma_kernel<N, D, false, 1>), fwd_grid(a, 4), FF_WAVE, stream, a);
   return FF_OK;
 }
 
@@ -1575,8 +1556,7 @@ static int dispatch_fwd(void* stream, int n, int d, const ff_fwd_args& a_in) {
     FF_MF(6, 2) FF_MF(2, 2) FF_MF(3, 2) FF_MF(4, 2) FF_MF(5, 2)
 #undef FF_MF
   }
-  const bool no_columns = n == 1 || n == 7 || n == 9 || n == 11 || d == 3;
-  if (MODE == 2 && (eloc_kind == 2 || no_columns || (eloc_kind == 0 && n >= 9))) {
+  if (MODE == 2 && (eloc_kind == 2 || ff_narrow_rows_only(n, d) || (eloc_kind == 0 && n >= 9))) {
 #define FF_RW(N_, D_, S_) if (n == N_ && d == D_) { launch_rows<N_, D_, S_>(stream, a); FF_LAUNCH_CHECK(); return FF_OK; }
     FF_RW(6, 2, 1) FF_RW(2, 2, 1) FF_RW(3, 2, 1) FF_RW(4, 2, 1) FF_RW(5, 2, 1) FF_RW(7, 2, 2) FF_RW(8, 2, 2) FF_RW(9, 2, 3)
     FF_RW(10, 2, 3) FF_RW(11, 2, 2) FF_RW(12, 2, 2) FF_RW(1, 2, 1)
@@ -1589,20 +1569,11 @@ static int dispatch_fwd(void* stream, int n, int d, const ff_fwd_args& a_in) {
 #undef FF_SP
   }
 #define FF_ND(N_, D_) if (n == N_ && d == D_) { const int s_ = launch_fwd<N_, D_, MODE>(stream, a); if (s_) return s_; FF_LAUNCH_CHECK(); return FF_OK; }
-  FF_ND(6, 2) FF_ND(3, 2) FF_ND(12, 2) FF_ND(2, 2) FF_ND(4, 2) FF_ND(5, 2) FF_ND(8, 2) FF_ND(10, 2)
-  if constexpr (MODE != 2) { FF_ND(1, 2) FF_ND(7, 2) FF_ND(9, 2) FF_ND(11, 2) FF_ND(2, 3) FF_ND(3, 3) FF_ND(4, 3) }   // (their local-energy pass is the row-layout kernel above)
+  FF_NARROW_COLUMNS(FF_ND)
+  if constexpr (MODE != 2) { FF_NARROW_ROWS_ONLY(FF_ND) }   // (their local-energy pass is the row-layout kernel above)
 #undef FF_ND
   // everything else: one walker per workgroup (ff_wide.hip: n <= 24, n d <= 60)
   return wide();
-}
-
-static int check_common(int64_t B, int n, int d, const ff_net* net, const ff_ode* ode) {
-  FF_CHECK(B >= 0 && n > 0 && d > 0 && net && ode, FF_EINVAL, "ff_cnf: bad argument");
-  FF_CHECK(net->He > 0 && net->ew1 && net->eb1 && net->ew2 && (net->Hm == 0 || (net->mw1 && net->mb1 && net->mw2)), FF_EINVAL,
-           "ff_cnf: bad net");
-  FF_CHECK(net->He <= FF_HMAX && net->Hm <= FF_HMAX, FF_EUNSUPPORTED, "ff_cnf: hidden width > 256");
-  FF_CHECK(ode->rtol > 0 && ode->atol > 0, FF_EINVAL, "ff_cnf: tolerances must be positive");
-  return FF_OK;
 }
 
 extern "C" {
@@ -1625,8 +1596,7 @@ size_t ff_radial_table_bytes(void) { return sizeof(double) * (size_t)FF_TAB_DOUB
 
 int ff_radial_table_build(void* stream, const ff_net* net, double* table) {
   FF_CHECK(net && table, FF_EINVAL, "ff_radial_table_build: null pointer");
-  FF_CHECK(net->He > 0 && net->ew1 && net->eb1 && net->ew2 && (net->Hm == 0 || (net->mw1 && net->mb1 && net->mw2)), FF_EINVAL,
-           "ff_radial_table_build: bad net");
+  if (const int st = ff_check_net("ff_radial_table_build", net)) return st;
   FF_LAUNCH(ff_table_kernel, FF_TAB_GRID, 128, stream, *net, table);
   FF_LAUNCH_CHECK();
   return FF_OK;
@@ -1634,30 +1604,22 @@ int ff_radial_table_build(void* stream, const ff_net* net, double* table) {
 
 int ff_cnf_generate(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* z,
                     double* x_out, int32_t* stats) {
-  int st = check_common(B, n, d, net, ode);
-  if (st) return st;
+  if (const int st = ff_check_flow("ff_cnf", B >= 0 && n > 0 && d > 0, net, ode)) return st;
   FF_CHECK(z && x_out, FF_EINVAL, "ff_cnf_generate: null pointer");
   if (B == 0) return FF_OK;
   ff_fwd_args a = {};
-  a.B = B; a.net = *net; a.ta = ode->t0; a.tb = ode->t1; a.rtol = ode->rtol; a.atol = ode->atol;
-  a.max_steps = ode->max_steps > 0 ? ode->max_steps : 10000;
-  a.wcost = ode->walker_cost; a.order = ode->walker_order;
-  a.h_init = ode->walker_h_init; a.h_scale = ode->walker_h_uniform ? -fabs(ode->walker_h_scale) : fabs(ode->walker_h_scale); a.h_out = ode->walker_h_out; a.h_equal = ode->walker_h_equal;
+  ff_fill_common(a, B, net, ode, true);
   a.y_in = z; a.y_out = x_out; a.stats = stats;
   return dispatch_fwd<0>(stream, n, d, a);
 }
 
 int ff_cnf_delta_logp(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* x,
                       double* z_out, double* dlogp_out, int32_t* stats) {
-  int st = check_common(B, n, d, net, ode);
-  if (st) return st;
+  if (const int st = ff_check_flow("ff_cnf", B >= 0 && n > 0 && d > 0, net, ode)) return st;
   FF_CHECK(x && z_out && dlogp_out, FF_EINVAL, "ff_cnf_delta_logp: null pointer");
   if (B == 0) return FF_OK;
   ff_fwd_args a = {};
-  a.B = B; a.net = *net; a.ta = ode->t1; a.tb = ode->t0; a.rtol = ode->rtol; a.atol = ode->atol;
-  a.max_steps = ode->max_steps > 0 ? ode->max_steps : 10000;
-  a.wcost = ode->walker_cost; a.order = ode->walker_order;
-  a.h_init = ode->walker_h_init; a.h_scale = ode->walker_h_uniform ? -fabs(ode->walker_h_scale) : fabs(ode->walker_h_scale); a.h_out = ode->walker_h_out; a.h_equal = ode->walker_h_equal;
+  ff_fill_common(a, B, net, ode, false);
   a.y_in = x; a.y_out = z_out; a.dl_out = dlogp_out; a.stats = stats;
   return dispatch_fwd<1>(stream, n, d, a);
 }
@@ -1686,16 +1648,12 @@ int ff_eloc_sensitivities(void* stream, int64_t B, int n, int d, const ff_net* n
 static int eloc_sensitivities_impl(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* x,
                                    void* workspace, int32_t* stats, const ff_fwd_args::ff_fin_args* fin) {
   t_eloc_fb = {false, false, nullptr, 0.0};
-  int st = check_common(B, n, d, net, ode);
-  if (st) return st;
+  if (const int st = ff_check_flow("ff_cnf", B >= 0 && n > 0 && d > 0, net, ode)) return st;
   FF_CHECK(x && workspace, FF_EINVAL, "ff_eloc_sensitivities: null pointer");
   if (B == 0) return FF_OK;
   ff_eloc_ws w = ff_eloc_carve(workspace, B, (size_t)n, (size_t)d, fin != nullptr && (fin->on & 2) && ff_eloc_ws_compact((size_t)n, (size_t)d));
   ff_fwd_args a = {};
-  a.B = B; a.net = *net; a.ta = ode->t1; a.tb = ode->t0; a.rtol = ode->rtol; a.atol = ode->atol;
-  a.max_steps = ode->max_steps > 0 ? ode->max_steps : 10000;
-  a.wcost = ode->walker_cost; a.order = ode->walker_order;
-  a.h_init = ode->walker_h_init; a.h_scale = ode->walker_h_uniform ? -fabs(ode->walker_h_scale) : fabs(ode->walker_h_scale); a.h_out = ode->walker_h_out; a.h_equal = ode->walker_h_equal;
+  ff_fill_common(a, B, net, ode, false);
   a.y_in = x; a.y_out = w.z0; a.dl_out = w.dl; a.Jt = w.Jt; a.kbar = w.kbar; a.dD = w.dD; a.Lpart = w.Lp; a.stats = stats;
   a.wclass = ode->walker_class; a.sens_class = ode->sens_tol_class;
   a.sens_w = ode->sens_tol > 1.0 ? 1.0 / ode->sens_tol : 1.0;
@@ -1724,15 +1682,13 @@ static int eloc_finish_impl(void* stream, int64_t B, int nup, int ndn, const int
                             double* glogp0_out, ff_fin_filter flt) {
   const int n = nup + ndn;
   FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && n > 0 && x && workspace, FF_EINVAL, "ff_eloc_finish: bad argument");
-  FF_CHECK((nup == 0 || tab_up) && (ndn == 0 || tab_dn), FF_EINVAL, "ff_eloc_finish: null orbital table");
-  FF_CHECK(nup <= FF_MAX_NS && ndn <= FF_MAX_NS, FF_EUNSUPPORTED, "ff_eloc_finish: determinant larger than FF_MAX_NS");
+  if (const int st = ff_check_spins("ff_eloc_finish", nup, ndn, tab_up, tab_dn)) return st;
   if (B == 0) return FF_OK;
-  const size_t M = (size_t)n * 2;
   ff_eloc_ws w = ff_eloc_carve((void*)workspace, B, (size_t)n, 2);
   FF_CHECK(2 * n <= FF_WAVE, FF_EUNSUPPORTED, "ff_eloc_finish: n*d > 64");
   {
     const int nsf = (nup == ndn || ndn == 0) ? nup : (nup == 0 ? ndn : 0);   // one determinant size for both spin species
-    const unsigned sgrid = (unsigned)((2 * B + 127) / 128);
+    const unsigned sgrid = ff_grid(2 * B, 128);
 #define FF_SF(NS_) case NS_: FF_LAUNCH((ff_eloc_slater_fixed_kernel<NS_>), sgrid, 128, stream, B, nup, ndn, tab_up, tab_dn, walker_state, (const double*)w.z0, w.Q, flt); break;
     switch (nsf) {
       FF_SF(1) FF_SF(2) FF_SF(3) FF_SF(4)
@@ -1743,19 +1699,15 @@ static int eloc_finish_impl(void* stream, int64_t B, int nup, int ndn, const int
   }
   FF_LAUNCH_CHECK();
   {
-    const int Gf = FF_WAVE / (2 * n);
-    const int64_t ng = (B + Gf - 1) / Gf;
     // (the filtered launch of the heavy route skips 99.6 % of the walker groups: a small grid striding over them instead of one
     // workgroup per group, whose starting and retiring alone took 26 us beside the throughput kernel)
     const int64_t gcap = flt.wclass ? 1024 : 32768;
-    FF_LAUNCH_LDS(ff_eloc_contract_kernel, (unsigned)(ng < gcap ? ng : gcap), FF_WAVE, ff_contract_lds_bytes(nup, ndn), stream, B, nup, ndn, Z, use_ho, x,
+    FF_LAUNCH_LDS(ff_eloc_contract_kernel, ff_grid(B, FF_WAVE / (2 * n), gcap), FF_WAVE, ff_contract_lds_bytes(nup, ndn), stream, B, nup, ndn, Z, use_ho, x,
               (const double*)w.Q, (const double*)w.Jt, (const double*)w.kbar, (const double*)w.dD, (const double*)w.dl,
               (const double*)w.Lp, logp, grad, lap, V, eloc, glogp0_out, flt);
   }
   FF_LAUNCH_CHECK();
-  if (z_out && hipMemcpyAsync(z_out, w.z0, sizeof(double) * (size_t)B * M, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
-  if (dlogp_out && hipMemcpyAsync(dlogp_out, w.dl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
-  return FF_OK;
+  return ff_copy_out(stream, B, (size_t)n * 2, w.z0, w.dl, z_out, dlogp_out);
 }
 
 extern "C" int ff_eloc_finish3d(void* stream, int64_t B, int nup, int ndn, const int32_t* tab_up, const int32_t* tab_dn,
@@ -1768,8 +1720,7 @@ int ff_eloc_nd(void* stream, int64_t B, int nup, int ndn, int d, const int32_t* 
                double* logp, double* grad, double* lap, double* V, double* eloc, double* z_out, double* dlogp_out,
                double* glogp0_out, void* workspace, int32_t* stats) {
   FF_CHECK(nup >= 0 && ndn >= 0 && nup + ndn > 0 && (d == 2 || d == 3), FF_EINVAL, "ff_eloc: bad particle numbers or dimension");
-  FF_CHECK((nup == 0 || tab_up) && (ndn == 0 || tab_dn), FF_EINVAL, "ff_eloc: null orbital table");
-  FF_CHECK(nup <= FF_MAX_NS && ndn <= FF_MAX_NS, FF_EUNSUPPORTED, "ff_eloc: determinant larger than FF_MAX_NS");
+  if (const int st = ff_check_spins("ff_eloc", nup, ndn, tab_up, tab_dn)) return st;
   // Offer the fused finish: a sensitivity kernel that implements it writes logp, grad, lap, V, E_loc and grad_z logp0 from its
   // epilogue, and J^T (8 M^2 bytes per walker) never leaves the chip -- the matrix-core kernel for nup = ndown <= 3 in d = 2 (bit 0:
   // config 2); on request (ff_ode::compact_finish: it costs time, include/fermiflow.h) the one-walker-per-workgroup kernels for every
@@ -1793,11 +1744,8 @@ int ff_eloc_nd(void* stream, int64_t B, int nup, int ndn, int d, const int32_t* 
                           z_out, dlogp_out, glogp0_out);
   }
   // (routed pass: the walkers of the heavy route were finished inside launch_routed -- by their own kernel's epilogue)
-  const size_t M = (size_t)n * d;
   ff_eloc_ws w = ff_eloc_carve(workspace, B, (size_t)n, (size_t)d, compact);
-  if (z_out && hipMemcpyAsync(z_out, w.z0, sizeof(double) * (size_t)B * M, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
-  if (dlogp_out && hipMemcpyAsync(dlogp_out, w.dl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
-  return FF_OK;
+  return ff_copy_out(stream, B, (size_t)n * d, w.z0, w.dl, z_out, dlogp_out);
 }
 
 int ff_eloc(void* stream, int64_t B, int nup, int ndn, const int32_t* tab_up, const int32_t* tab_dn,

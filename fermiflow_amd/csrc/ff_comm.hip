@@ -5,12 +5,10 @@
 //
 // RCCL is bound at run time -- dlopen of the copy the process already holds (torch's) or librccl.so.1 -- so that loading
 // libfermiflow_hip.so never pulls a second RCCL into a process, and a single-GPU user never loads one at all.
-#include "ff_common.h"
+#include "ff_host.h"
 #include <dlfcn.h>
 #include <stdlib.h>
 #include <string.h>
-
-extern void ff_set_error(const char* msg);
 
 namespace {
 

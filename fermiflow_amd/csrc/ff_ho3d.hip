@@ -714,10 +714,7 @@ ff_rng_fill3d_kernel(int64_t B, int n, int steps, uint64_t seed, int64_t woff, d
 }
 
 // =================================================================================================
-extern void ff_set_error(const char* msg);
-#define FF_CHECK(cond, code, msg) do { if (!(cond)) { ff_set_error(msg); return code; } } while (0)
-#define FF_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { ff_set_error(hipGetErrorString(e_)); return FF_ELAUNCH; } } while (0)
-static unsigned ff3_grid(int64_t B, int block) { return (unsigned)((B + block - 1) / block); }
+#include "ff_host.h"
 
 extern "C" {
 
@@ -725,9 +722,9 @@ int ff_logprob3d(void* stream, int64_t B, int nup, int ndn, const int32_t* tab_u
                  const int32_t* walker_state, const double* x, double* logp, double* grad, double* lap) {
   FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && nup + ndn > 0 && x && logp, FF_EINVAL, "ff_logprob3d: bad argument");
   FF_CHECK((nup == 0 || tab_up) && (ndn == 0 || tab_dn) && ((grad == nullptr) == (lap == nullptr)), FF_EINVAL, "ff_logprob3d: null pointer");
-  FF_CHECK(nup <= FF_MAX_NS && ndn <= FF_MAX_NS, FF_EUNSUPPORTED, "ff_logprob3d: determinant larger than FF_MAX_NS");
+  if (const int st = ff_check_det_size("ff_logprob3d", nup, ndn)) return st;
   if (B == 0) return FF_OK;
-  FF_LAUNCH(ff_logprob3d_kernel, ff3_grid(B, 64), 64, stream, B, nup, ndn, tab_up, tab_dn, walker_state, x, logp, grad, lap);
+  FF_LAUNCH(ff_logprob3d_kernel, ff_grid(B, 64), 64, stream, B, nup, ndn, tab_up, tab_dn, walker_state, x, logp, grad, lap);
   FF_LAUNCH_CHECK();
   return FF_OK;
 }
@@ -737,8 +734,7 @@ int ff_mcmc_sample_noise3d(void* stream, int64_t B, int nup, int ndn, const int3
                            double* x_out, double* logp_out, uint8_t* accept) {
   FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && nup + ndn > 0 && steps >= 0 && x_out && g0 && (steps == 0 || (g && u)), FF_EINVAL,
            "ff_mcmc_sample_noise3d: bad argument");
-  FF_CHECK((nup == 0 || tab_up) && (ndn == 0 || tab_dn), FF_EINVAL, "ff_mcmc_sample_noise3d: null orbital table");
-  FF_CHECK(nup <= FF_MAX_NS && ndn <= FF_MAX_NS, FF_EUNSUPPORTED, "ff_mcmc_sample_noise3d: determinant larger than FF_MAX_NS");
+  if (const int st = ff_check_spins("ff_mcmc_sample_noise3d", nup, ndn, tab_up, tab_dn)) return st;
   if (B == 0) return FF_OK;
   return ff_mcmc_rows_launch(stream, 3, true, B, nup, ndn, tab_up, tab_dn, walker_state, steps, tau, g0, g, u, (uint64_t)0, (int64_t)0, x_out,
                              logp_out, accept, (int*)nullptr);
@@ -748,8 +744,7 @@ int ff_mcmc_sample3d(void* stream, int64_t B, int nup, int ndn, const int32_t* t
                      const int32_t* walker_state, int steps, double tau, uint64_t seed, int64_t walker_offset,
                      double* x_out, double* logp_out, int32_t* accept_count) {
   FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && nup + ndn > 0 && steps >= 0 && x_out, FF_EINVAL, "ff_mcmc_sample3d: bad argument");
-  FF_CHECK((nup == 0 || tab_up) && (ndn == 0 || tab_dn), FF_EINVAL, "ff_mcmc_sample3d: null orbital table");
-  FF_CHECK(nup <= FF_MAX_NS && ndn <= FF_MAX_NS, FF_EUNSUPPORTED, "ff_mcmc_sample3d: determinant larger than FF_MAX_NS");
+  if (const int st = ff_check_spins("ff_mcmc_sample3d", nup, ndn, tab_up, tab_dn)) return st;
   if (B == 0) return FF_OK;
   return ff_mcmc_rows_launch(stream, 3, false, B, nup, ndn, tab_up, tab_dn, walker_state, steps, tau, (const double*)nullptr,
                              (const double*)nullptr, (const double*)nullptr, seed, walker_offset, x_out, logp_out, (uint8_t*)nullptr, accept_count);
@@ -758,18 +753,17 @@ int ff_mcmc_sample3d(void* stream, int64_t B, int nup, int ndn, const int32_t* t
 int ff_rng_fill3d(void* stream, int64_t B, int n, int steps, uint64_t seed, int64_t walker_offset, double* g0, double* g, double* u) {
   FF_CHECK(B >= 0 && n > 0 && n <= 2 * FF_MAX_NS && steps >= 0 && g0 && (steps == 0 || (g && u)), FF_EINVAL, "ff_rng_fill3d: bad argument");
   if (B == 0) return FF_OK;
-  FF_LAUNCH(ff_rng_fill3d_kernel, ff3_grid(B, 128), 128, stream, B, n, steps, seed, walker_offset, g0, g, u);
+  FF_LAUNCH(ff_rng_fill3d_kernel, ff_grid(B, 128), 128, stream, B, n, steps, seed, walker_offset, g0, g, u);
   FF_LAUNCH_CHECK();
   return FF_OK;
 }
 
 int ff_backflow_v_div_f32(void* stream, int64_t B, int n, int d, const ff_net* net, const double* x, double* v, double* div) {
   FF_CHECK(B >= 0 && n > 0 && d > 0 && net && x && (v || div), FF_EINVAL, "ff_backflow_v_div_f32: bad argument");
-  FF_CHECK(net->He > 0 && net->ew1 && net->eb1 && net->ew2 && (net->Hm == 0 || (net->mw1 && net->mb1 && net->mw2)), FF_EINVAL,
-           "ff_backflow_v_div_f32: bad net");
+  if (const int st = ff_check_net("ff_backflow_v_div_f32", net)) return st;
   FF_CHECK(n <= 24 && d <= 3, FF_EUNSUPPORTED, "ff_backflow_v_div_f32: n > 24 or d > 3");
   if (B == 0) return FF_OK;
-  FF_LAUNCH(ff_backflow_f32_kernel, ff3_grid(B, 128), 128, stream, B, n, d, *net, x, v, div);
+  FF_LAUNCH(ff_backflow_f32_kernel, ff_grid(B, 128), 128, stream, B, n, d, *net, x, v, div);
   FF_LAUNCH_CHECK();
   return FF_OK;
 }
@@ -781,28 +775,23 @@ int ff_eloc_finish3d(void* stream, int64_t B, int nup, int ndn, const int32_t* t
                      double* glogp0_out) {
   const int n = nup + ndn;
   FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && n > 0 && x && workspace, FF_EINVAL, "ff_eloc_finish3d: bad argument");
-  FF_CHECK((nup == 0 || tab_up) && (ndn == 0 || tab_dn), FF_EINVAL, "ff_eloc_finish3d: null orbital table");
+  if (const int st = ff_check_tables("ff_eloc_finish3d", nup, ndn, tab_up, tab_dn)) return st;
   FF_CHECK(nup <= FF_MAX_NS && ndn <= FF_MAX_NS && 3 * n <= FF_WAVE, FF_EUNSUPPORTED, "ff_eloc_finish3d: walker too large");
   if (B == 0) return FF_OK;
-  const size_t M = (size_t)n * 3;
   ff_eloc_ws w = ff_eloc_carve((void*)workspace, B, (size_t)n, 3);
   if (ff_slater_rows_launch(stream, 3, B, nup, ndn, tab_up, tab_dn, walker_state, (const double*)w.z0, w.Q) != FF_OK) return FF_ELAUNCH;
   if (3 * n > 32) {      // a walker per workgroup, four lanes per direction
     const size_t lds = sizeof(double) * ((size_t)9 * n * n + (size_t)(3 * n + 6 * n + 3 * (nup * nup + ndn * ndn) + 2) + 4 * FF_WAVE);
-    FF_LAUNCH_LDS(ff_wide_contract3d_kernel, (unsigned)(B < 65536 ? B : 65536), 4 * FF_WAVE, lds, stream, B, nup, ndn, Z, use_ho, x,
+    FF_LAUNCH_LDS(ff_wide_contract3d_kernel, ff_grid(B, 1, 65536), 4 * FF_WAVE, lds, stream, B, nup, ndn, Z, use_ho, x,
                   (const double*)w.Q, (const double*)w.Jt, (const double*)w.kbar, (const double*)w.dD, (const double*)w.dl,
                   (const double*)w.Lp, logp, grad, lap, V, eloc, glogp0_out);
   } else {
-    const int Gf = FF_WAVE / (3 * n);
-    const int64_t ng = (B + Gf - 1) / Gf;
-    FF_LAUNCH_LDS(ff_eloc_contract3d_kernel, (unsigned)(ng < 32768 ? ng : 32768), FF_WAVE, ff_contract3d_lds_bytes(nup, ndn), stream, B, nup, ndn, Z,
+    FF_LAUNCH_LDS(ff_eloc_contract3d_kernel, ff_grid(B, FF_WAVE / (3 * n), 32768), FF_WAVE, ff_contract3d_lds_bytes(nup, ndn), stream, B, nup, ndn, Z,
                   use_ho, x, (const double*)w.Q, (const double*)w.Jt, (const double*)w.kbar, (const double*)w.dD, (const double*)w.dl,
                   (const double*)w.Lp, logp, grad, lap, V, eloc, glogp0_out);
   }
   FF_LAUNCH_CHECK();
-  if (z_out && hipMemcpyAsync(z_out, w.z0, sizeof(double) * (size_t)B * M, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
-  if (dlogp_out && hipMemcpyAsync(dlogp_out, w.dl, sizeof(double) * (size_t)B, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
-  return FF_OK;
+  return ff_copy_out(stream, B, (size_t)n * 3, w.z0, w.dl, z_out, dlogp_out);
 }
 
 }  // extern "C"

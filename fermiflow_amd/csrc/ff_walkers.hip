@@ -1229,10 +1229,7 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
 // =================================================================================================
 // C ABI
 // =================================================================================================
-extern void ff_set_error(const char* msg);
-#define FF_CHECK(cond, code, msg) do { if (!(cond)) { ff_set_error(msg); return code; } } while (0)
-#define FF_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { ff_set_error(hipGetErrorString(e_)); return FF_ELAUNCH; } } while (0)
-static inline unsigned ff_grid(int64_t B, int block) { return (unsigned)((B + block - 1) / block); }
+#include "ff_host.h"
 
 template <int NU, int ND>
 static void launch_mcmc(bool noise, void* stream, int64_t B, int nup, int ndn, const int* tu, const int* td, const int* ws,
@@ -1275,7 +1272,7 @@ static int mcmc_dispatch(bool noise, void* stream, int64_t B, int nup, int ndn, 
                          int steps, double tau, const double* g0, const double* g, const double* u, uint64_t seed, int64_t woff,
                          double* x_out, double* logp_out, uint8_t* accept, int* acc_count) {
   FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && nup + ndn > 0 && steps >= 0, FF_EINVAL, "ff_mcmc: bad sizes");
-  FF_CHECK(nup <= FF_MAX_NS && ndn <= FF_MAX_NS, FF_EUNSUPPORTED, "ff_mcmc: determinant larger than FF_MAX_NS");
+  if (const int st = ff_check_det_size("ff_mcmc", nup, ndn)) return st;
   FF_CHECK(x_out && (nup == 0 || tu) && (ndn == 0 || td), FF_EINVAL, "ff_mcmc: null pointer");
   FF_CHECK(!noise || (g0 && (steps == 0 || (g && u))), FF_EINVAL, "ff_mcmc: null noise pointer");
   if (B == 0) return FF_OK;
@@ -1597,8 +1594,7 @@ int ff_slater_logabsdet_bwd(void* stream, int64_t B, int n, const int32_t* orb_t
 int ff_logprob(void* stream, int64_t B, int nup, int ndn, const int32_t* tab_up, const int32_t* tab_dn,
                const int32_t* walker_state, const double* x, double* logp, double* grad, double* lap) {
   FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && nup + ndn > 0 && x && logp, FF_EINVAL, "ff_logprob: bad argument");
-  FF_CHECK((nup == 0 || tab_up) && (ndn == 0 || tab_dn), FF_EINVAL, "ff_logprob: null orbital table");
-  FF_CHECK(nup <= FF_MAX_NS && ndn <= FF_MAX_NS, FF_EUNSUPPORTED, "ff_logprob: determinant larger than FF_MAX_NS");
+  if (const int st = ff_check_spins("ff_logprob", nup, ndn, tab_up, tab_dn)) return st;
   if (B == 0) return FF_OK;
   {
     const int nsf = (nup == ndn || ndn == 0) ? nup : (nup == 0 ? ndn : 0);   // one determinant size for both spin species
@@ -1636,8 +1632,7 @@ int ff_mlp_eval_nd(void* stream, int64_t N, int D_in, int H, const double* w1, c
 
 int ff_backflow_vjp(void* stream, int64_t B, int n, int d, const ff_net* net, const double* x, const double* w, double* Aw, double* gdiv) {
   FF_CHECK(B >= 0 && n > 0 && d > 0 && net && x && ((w && Aw) || gdiv) && (Aw == nullptr || w != nullptr), FF_EINVAL, "ff_backflow_vjp: bad argument");
-  FF_CHECK(net->He > 0 && net->ew1 && net->eb1 && net->ew2 && (net->Hm == 0 || (net->mw1 && net->mb1 && net->mw2)), FF_EINVAL,
-           "ff_backflow_vjp: bad net");
+  if (const int st = ff_check_net("ff_backflow_vjp", net)) return st;
   FF_CHECK(n <= FF_MAX_N && d <= 3, FF_EUNSUPPORTED, "ff_backflow_vjp: n > 24 or d > 3");
   if (B == 0) return FF_OK;
   FF_LAUNCH(ff_backflow_vjp_kernel, ff_grid(B, 128), 128, stream, B, n, d, *net, x, w, Aw, gdiv);
@@ -1647,8 +1642,7 @@ int ff_backflow_vjp(void* stream, int64_t B, int n, int d, const ff_net* net, co
 
 int ff_backflow_v_div(void* stream, int64_t B, int n, int d, const ff_net* net, const double* x, double* v, double* div) {
   FF_CHECK(B >= 0 && n > 0 && d > 0 && net && x && (v || div), FF_EINVAL, "ff_backflow_v_div: bad argument");
-  FF_CHECK(net->He > 0 && net->ew1 && net->eb1 && net->ew2 && (net->Hm == 0 || (net->mw1 && net->mb1 && net->mw2)), FF_EINVAL,
-           "ff_backflow_v_div: bad net");
+  if (const int st = ff_check_net("ff_backflow_v_div", net)) return st;
   FF_CHECK(n <= FF_MAX_N && d <= 3, FF_EUNSUPPORTED, "ff_backflow_v_div: n > 24 or d > 3");
   if (B == 0) return FF_OK;
   FF_LAUNCH(ff_backflow_kernel, ff_grid(B, 128), 128, stream, B, n, d, *net, x, v, div);
@@ -1661,8 +1655,7 @@ int ff_potential(void* stream, int64_t B, int n, int d, double Z, int use_ho, co
   FF_CHECK(n <= FF_MAX_N && d <= 3, FF_EUNSUPPORTED, "ff_potential: n > 24 or d > 3");
   if (B == 0) return FF_OK;
   {
-    const int64_t ntiles = (B + FF_WAVE - 1) / FF_WAVE;
-    const unsigned pgrid = (unsigned)(ntiles < 65536 ? ntiles : 65536);
+    const unsigned pgrid = ff_grid(B, FF_WAVE, 65536);
 #define FF_PS(N_, D_) if (n == N_ && d == D_) { FF_LAUNCH((ff_potential_stream_kernel<N_, D_>), pgrid, FF_WAVE, stream, B, Z, use_ho, x, V); FF_LAUNCH_CHECK(); return FF_OK; }
     FF_PS(6, 2) FF_PS(12, 2) FF_PS(3, 2) FF_PS(2, 2) FF_PS(4, 2) FF_PS(5, 2) FF_PS(8, 2) FF_PS(10, 2) FF_PS(6, 3) FF_PS(4, 3)
 #undef FF_PS
@@ -1700,7 +1693,7 @@ __global__ void __launch_bounds__(FF_ORD_THREADS) ff_scale_counts_kernel(int64_t
 int ff_scale_counts(void* stream, int64_t B, const int32_t* cost, const double* hs, const double* he, double interval, double* counts128) {
   FF_CHECK(B >= 0 && counts128 && (B == 0 || (cost && hs && he)), FF_EINVAL, "ff_scale_counts: bad argument");
   if (B == 0) return FF_OK;
-  FF_LAUNCH(ff_scale_counts_kernel, (unsigned)((B + FF_ORD_SEG - 1) / FF_ORD_SEG), FF_ORD_THREADS, stream, B, cost, hs, he, interval, counts128);
+  FF_LAUNCH(ff_scale_counts_kernel, ff_grid(B, FF_ORD_SEG), FF_ORD_THREADS, stream, B, cost, hs, he, interval, counts128);
   FF_LAUNCH_CHECK();
   return FF_OK;
 }
@@ -1797,7 +1790,7 @@ int ff_energy_estimate(void* stream, int64_t B, const double* e, const double* l
                        double* sums4, double* est3, void* workspace) {
   FF_CHECK(B > 0 && e && logp && shift_dev && sums4 && workspace && n_global >= 0 && (n_global == 0 || est3), FF_EINVAL,
            "ff_energy_estimate: bad argument");
-  const unsigned nb = (unsigned)((B + FF_EST_SEG - 1) / FF_EST_SEG);
+  const unsigned nb = ff_grid(B, FF_EST_SEG);
   double* part = (double*)workspace + 1;       // [0]: the counter (zero between calls) | partial sums
   FF_LAUNCH(ff_energy_estimate_kernel, nb, FF_RBLOCK(FF_EST_THREADS), stream, B, e, logp, shift_dev, (double)n_global, sums4, est3, part,
             (unsigned*)workspace);

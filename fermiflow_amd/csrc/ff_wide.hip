@@ -975,8 +975,8 @@ ff_wide_eloc_kernel(ff_fwd_args A, int n) {
 }
 
 // =====================================================================================================================
-extern void ff_set_error(const char* msg);
-#define FF_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { ff_set_error(hipGetErrorString(e_)); return FF_ELAUNCH; } } while (0)
+#include "ff_host.h"
+#include <type_traits>
 
 static std::atomic<int> g_family{-1};   // -1: not decided yet (FF_WIDE in the environment), 0: by particle number, 1: wide for all
 bool ff_wide_forced() {
@@ -1005,42 +1005,32 @@ int ff_wide_supported(int n, int d) {
   return (d == 2 || d == 3) && n >= 1 && n <= FF_WIDE_NMAX && n * d <= FF_WIDE_MMAX;
 }
 
-static int64_t wide_cus() {
-  static int64_t n = 0;
-  if (n == 0) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    n = cus;
-  }
-  return n;
-}
-
 template <int D, int MODE>
 static void launch_wide_flow(void* stream, const ff_fwd_args& a, int n) {
-  const unsigned grid = (unsigned)(a.B < 64 * wide_cus() ? a.B : 64 * wide_cus());
+  const unsigned grid = ff_grid(a.B, 1, 64 * ff_device_cus());
   if (a.evt) FF_LAUNCH((ff_wide_flow_kernel<D, MODE, true>), grid, FF_WAVE, stream, a, n);
   FF_LAUNCH((ff_wide_flow_kernel<D, MODE, false>), grid, FF_WAVE, stream, a, n);
 }
 
-template <int D, int T>
+// launch(std::bool_constant<FIN>): FIN = the local-energy kernels finish their walkers in their epilogue (bit 1 of fin.on:
+// ff_ode::compact_finish, the heavy route).  The FF_WIDE_NO_FIN build has no such instantiations.
+template <class F>
+static void wide_with_fin(const ff_fwd_args& a, F launch) {
+#ifndef FF_WIDE_NO_FIN
+  if (a.fin.on & 2) { launch(std::true_type()); return; }
+#endif
+  launch(std::false_type());
+}
+
+template <int D, int T, bool FIN>
 static void launch_wide_eloc(void* stream, const ff_fwd_args& a, int n) {
   // persistent grid when the launch has a work queue: as many workgroups as stay resident (one per CU at T = 4)
   const int64_t per_cu = T >= 3 ? 1 : (T == 2 ? 2 : 4);
-  const int64_t cap = a.queue ? per_cu * wide_cus() : ((int64_t)1 << 20);
-  const unsigned grid = (unsigned)(a.B < cap ? a.B : cap);
+  const unsigned grid = ff_grid(a.B, 1, a.queue ? per_cu * ff_device_cus() : ((int64_t)1 << 20));
   // single-precision sensitivities (ff_set_sens_precision(32)): the table kernel with J, A, S in fp32; its fallback stays fp64
-#ifndef FF_WIDE_NO_FIN
-  if (a.fin.on & 2) {      // fused finish (ff_ode::compact_finish)
-    if (a.evt && ff_wide_sens_fp32() && T >= 2) FF_LAUNCH((ff_wide_eloc_kernel<D, (T >= 2 ? T : 2), true, float, true>), grid, FF_WAVE * T, stream, a, n);
-    else if (a.evt) FF_LAUNCH((ff_wide_eloc_kernel<D, T, true, double, true>), grid, FF_WAVE * T, stream, a, n);
-    FF_LAUNCH((ff_wide_eloc_kernel<D, T, false, double, true>), grid, FF_WAVE * T, stream, a, n);
-    return;
-  }
-#endif
-  if (a.evt && ff_wide_sens_fp32() && T >= 2) FF_LAUNCH((ff_wide_eloc_kernel<D, (T >= 2 ? T : 2), true, float, false>), grid, FF_WAVE * T, stream, a, n);
-  else if (a.evt) FF_LAUNCH((ff_wide_eloc_kernel<D, T, true, double, false>), grid, FF_WAVE * T, stream, a, n);
-  FF_LAUNCH((ff_wide_eloc_kernel<D, T, false, double, false>), grid, FF_WAVE * T, stream, a, n);
+  if (a.evt && ff_wide_sens_fp32() && T >= 2) FF_LAUNCH((ff_wide_eloc_kernel<D, (T >= 2 ? T : 2), true, float, FIN>), grid, FF_WAVE * T, stream, a, n);
+  else if (a.evt) FF_LAUNCH((ff_wide_eloc_kernel<D, T, true, double, FIN>), grid, FF_WAVE * T, stream, a, n);
+  FF_LAUNCH((ff_wide_eloc_kernel<D, T, false, double, FIN>), grid, FF_WAVE * T, stream, a, n);
 }
 
 int ff_wide_eloc_heavy(void* stream, int n, int d, const ff_fwd_args& a, int64_t max_groups) {
@@ -1048,15 +1038,11 @@ int ff_wide_eloc_heavy(void* stream, int n, int d, const ff_fwd_args& a, int64_t
 #ifdef FF_WIDE_NO_FIN      // (diagnostic build without the fused-finish instantiations: a caller that counts on them must hear it -- ADVICE r04)
   if (a.fin.on & 2) { ff_set_error("this build (FF_WIDE_NO_FIN) has no fused finish: ff_ode.compact_finish is not available"); return FF_EUNSUPPORTED; }
 #endif
-  const unsigned grid = (unsigned)(a.B < max_groups ? a.B : max_groups);
-#ifndef FF_WIDE_NO_FIN
-  if (a.fin.on & 2) {
-    if (d == 2) FF_LAUNCH((ff_wide_eloc_kernel<2, 1, true, double, true>), grid, FF_WAVE, stream, a, n);
-    else FF_LAUNCH((ff_wide_eloc_kernel<3, 1, true, double, true>), grid, FF_WAVE, stream, a, n);
-  } else
-#endif
-  if (d == 2) FF_LAUNCH((ff_wide_eloc_kernel<2, 1, true, double, false>), grid, FF_WAVE, stream, a, n);
-  else FF_LAUNCH((ff_wide_eloc_kernel<3, 1, true, double, false>), grid, FF_WAVE, stream, a, n);
+  const unsigned grid = ff_grid(a.B, 1, max_groups);
+  wide_with_fin(a, [&](auto fin) {
+    if (d == 2) FF_LAUNCH((ff_wide_eloc_kernel<2, 1, true, double, decltype(fin)::value>), grid, FF_WAVE, stream, a, n);
+    else FF_LAUNCH((ff_wide_eloc_kernel<3, 1, true, double, decltype(fin)::value>), grid, FF_WAVE, stream, a, n);
+  });
   FF_LAUNCH_CHECK();
   return FF_OK;
 }
@@ -1073,7 +1059,7 @@ int ff_wide_dispatch_fwd(int mode, void* stream, int n, int d, const ff_fwd_args
   else if (mode == 1) { if (d == 2) launch_wide_flow<2, 1>(stream, a, n); else launch_wide_flow<3, 1>(stream, a, n); }
   else {
     const int T = (n * d + 4 + 15) / 16;
-#define FF_WE(D_, T_) if (d == D_ && T == T_) launch_wide_eloc<D_, T_>(stream, a, n);
+#define FF_WE(D_, T_) if (d == D_ && T == T_) wide_with_fin(a, [&](auto fin) { launch_wide_eloc<D_, T_, decltype(fin)::value>(stream, a, n); });
     FF_WE(2, 1) FF_WE(2, 2) FF_WE(2, 3) FF_WE(2, 4) FF_WE(3, 1) FF_WE(3, 2) FF_WE(3, 3) FF_WE(3, 4)
 #undef FF_WE
   }

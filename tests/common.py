@@ -233,7 +233,7 @@ def make_flow(eta, mu, dev):
 FF_WAVE = 64
 ADJ_WPW = 2          # ff_cnf_adj.hip:213  FF_ADJ_WPW: waves per workgroup of the tabulated adjoint, each with its own walker groups
 ADJ_G12 = 3          # ff_cnf_adj.hip:220  FF_ADJ_G12: walkers per wave of the tabulated adjoint at n d = 12
-MFMA_WPS = 2         # ff_cnf_fwd.hip:1517 FF_MFMA_WPS: the matrix-core kernel's cap is this many times fwd_queue_blocks()
+MFMA_WPS = 2         # ff_cnf_fwd.hip FF_MFMA_WPS: the matrix-core kernel's cap is this many times the persistent grid of fwd_grid()
 FWD_FB_GRID = 2048   # ff_cnf_fwd.hip:1487 grid-stride cap of the direct fallback behind a flow table kernel
 ROWS_SPLIT = {1: 1, 2: 1, 3: 1, 4: 1, 5: 1, 6: 1, 7: 2, 8: 2, 9: 3, 10: 3, 11: 2, 12: 2}   # ff_cnf_fwd.hip:1581 FF_RW
 
@@ -243,7 +243,7 @@ def cu_count(hostsim=False):
     return 2 if hostsim else torch.cuda.get_device_properties(0).multi_processor_count
 
 
-def _geom_G(n, d):      # ff_ode.h ff_geom<N, D>::G = ff_cnf_adj.hip:800 adj_G: walkers per wave of the narrow kernels
+def _geom_G(n, d):      # ff_ode.h ff_geom_G = ff_geom<N, D>::G: walkers per wave of the narrow kernels
     M = n * d
     return min(16, FF_WAVE // M)
 
@@ -258,7 +258,7 @@ def _adjtab_G(n, d):    # ff_cnf_adj.hip:227 ff_adjtab_G
     return g
 
 
-def _narrow(n, d):      # ff_cnf_adj.hip:867 adj_is_wide; ff_cnf_fwd.hip:1593 (flow kernels): the same particle numbers
+def _narrow(n, d):      # ff_ode.h ff_narrow_shape: the shapes of FF_NARROW_COLUMNS and FF_NARROW_ROWS_ONLY
     return (d == 2 and 1 <= n <= 12) or (d == 3 and 2 <= n <= 4)
 
 
@@ -267,7 +267,7 @@ def kernel_families(call, n, d, cus, hostsim=False):
     with a radial-table net and every radius on the table: call = "flow" (cnf_generate / cnf_delta_logp), "eloc" (ff_eloc_nd,
     queue mode), "adjoint"; "flow_fb", "eloc_fb", "adj_fb" = the direct kernels that redo the call when a radius is off the table.
     The host simulator builds with FF_MFMA_FROM=99 (tests/hostsim/Makefile): no matrix-core local-energy kernel there."""
-    q = 4 * cus                                     # ff_cnf_fwd.hip:1347 fwd_queue_blocks(), ff_cnf_adj.hip:804 adj_default_blocks()
+    q = 4 * cus                                     # ff_cnf_fwd.hip fwd_grid(), ff_cnf_adj.hip adj_grid(): four waves per CU (ff_api.hip ff_device_cus)
     if call in ("flow", "flow_fb"):
         if not _narrow(n, d):                       # ff_wide.hip:1020 launch_wide_flow: one walker per workgroup, 64 per CU
             return {"flow_wide": (1, 64 * cus)}
@@ -288,7 +288,7 @@ def kernel_families(call, n, d, cus, hostsim=False):
         return {"eloc_wide": (1, per_cu * cus)}
     if d == 2 and 4 <= n <= 6 and not hostsim:      # ff_cnf_fwd.hip:1521 launch_mfma: four walkers per wave
         return {"eloc_mfma": (4, (MFMA_WPS if call == "eloc" else 1) * q * 4)}
-    if d == 3 or n in (1, 7, 9, 10, 11):            # ff_cnf_fwd.hip:1578 no_columns, 1507 launch_rows
+    if d == 3 or n in (1, 7, 9, 10, 11):            # ff_ode.h ff_narrow_rows_only (and n = 10: FF_RW), ff_cnf_fwd.hip launch_rows
         G = min(16, FF_WAVE // (M * (ROWS_SPLIT[n] if d == 2 else 1)))
         return {"eloc_rows": (G, q * G)}
     if n == 8:                                      # ff_cnf_fwd.hip:1495 launch_split

@@ -352,3 +352,104 @@ def test_stiff_regimes_cover_every_grid_row_length_and_refusal():
         eta, mu = stiff_net(target, stiff=stiff)
         top = eta if stiff == "eta" else mu
         assert np.abs(top[0]).max() == target and max(np.abs(eta[0]).max(), np.abs(mu[0]).max()) == target, r
+
+
+def test_argument_refusals_keep_their_status_and_text():
+    """Status code and full ff_last_error() text of every refusal that the entry points share through the argument validators of
+    csrc/ff_host.h (net complete, hidden width, tolerances, orbital tables, determinant size) and of the shape refusals beside them.
+    Callers match on these strings (fermiflow_amd/_lib.py check() passes them on).  Every call here is refused before anything is
+    launched, so it runs without a GPU and is harmless with one; the pointers are never dereferenced."""
+    import ctypes as C
+    from fermiflow_amd import _lib
+    lib = _lib.lib()
+    p8, i64, f64 = C.c_void_p(8), C.c_int64, C.c_double
+    B = i64(4)
+    net_ok = _lib.FFNet(50, p8, p8, p8, 50, p8, p8, p8)
+    bad_nets = [_lib.FFNet(50, None, p8, p8, 0, None, None, None), _lib.FFNet(50, p8, None, p8, 0, None, None, None),
+                _lib.FFNet(50, p8, p8, None, 50, p8, p8, p8), _lib.FFNet(0, p8, p8, p8, 0, None, None, None),
+                _lib.FFNet(50, p8, p8, p8, 50, None, p8, p8), _lib.FFNet(50, p8, p8, p8, 50, p8, p8, None)]
+    wide_nets = [_lib.FFNet(300, p8, p8, p8, 50, p8, p8, p8), _lib.FFNet(50, p8, p8, p8, 300, p8, p8, p8)]
+    ode_ok = _lib.FFOde(0.0, 1.0, 1e-6, 1e-8, 0)
+    bad_odes = [_lib.FFOde(0.0, 1.0, 0.0, 1e-8, 0), _lib.FFOde(0.0, 1.0, 1e-6, -1.0, 0)]
+    r = C.byref
+
+    def refused(status, text, fn, *args):
+        got = getattr(lib, fn)(None, *args)
+        assert (got, lib.ff_last_error().decode()) == (status, text), (fn, got, lib.ff_last_error())
+
+    # --- ff_net / ff_ode of the flow entry points: complete net (1), hidden width (2), tolerances (1), in that order
+    flow = {
+        "ff_cnf_generate": lambda n, o, nn=6, d=2: (B, nn, d, n, o, p8, p8, None),
+        "ff_cnf_delta_logp": lambda n, o, nn=6, d=2: (B, nn, d, n, o, p8, p8, p8, None),
+        "ff_eloc_sensitivities": lambda n, o, nn=6, d=2: (B, nn, d, n, o, p8, p8, None),
+        "ff_eloc_nd": lambda n, o: (B, 3, 3, 2, p8, p8, None, n, o, f64(2.0), 1, p8, p8, p8, p8, p8, p8, p8, p8, p8, p8, None),
+        "ff_eloc": lambda n, o: (B, 3, 3, p8, p8, None, n, o, f64(2.0), 1, p8, p8, p8, p8, p8, p8, p8, p8, p8, p8, None),
+    }
+    adjoint = {
+        "ff_cnf_adjoint": lambda n, o, nn=6, d=2, gp=p8: (B, nn, d, n, o, p8, p8, p8, None, gp, p8, None),
+        "ff_cnf_adjoint_energy": lambda n, o, nn=6, d=2, gp=p8: (B, nn, d, n, o, p8, p8, p8, p8, None, f64(0.25), None, gp, p8, None),
+    }
+    for who, fns in (("ff_cnf", flow), ("ff_cnf_adjoint", adjoint)):
+        for fn, args in fns.items():
+            for net in bad_nets:
+                refused(1, f"{who}: bad net", fn, *args(r(net), r(ode_ok)))
+                refused(1, f"{who}: bad net", fn, *args(r(net), r(bad_odes[0])))          # the net is looked at first
+            for net in wide_nets:
+                refused(2, f"{who}: hidden width > 256", fn, *args(r(net), r(ode_ok)))
+                refused(2, f"{who}: hidden width > 256", fn, *args(r(net), r(bad_odes[1])))   # ... and its width before the tolerances
+            for ode in bad_odes:
+                refused(1, f"{who}: tolerances must be positive", fn, *args(r(net_ok), r(ode)))
+            refused(1, f"{who}: bad argument", fn, *args(None, r(ode_ok)))
+            refused(1, f"{who}: bad argument", fn, *args(r(net_ok), None))
+    for fn in ("ff_cnf_generate", "ff_cnf_delta_logp", "ff_eloc_sensitivities"):
+        refused(1, "ff_cnf: bad argument", fn, *flow[fn](r(bad_nets[0]), r(ode_ok), 0, 2))
+        refused(1, "ff_cnf: bad argument", fn, *flow[fn](r(net_ok), r(ode_ok), 6, 0))
+    for fn in adjoint:
+        refused(1, "ff_cnf_adjoint: bad argument", fn, *adjoint[fn](r(bad_nets[0]), r(ode_ok), 6, 2, None))   # grad_params missing
+        refused(2, "ff_cnf_adjoint: n*d > 64", fn, *adjoint[fn](r(net_ok), r(ode_ok), 33, 2))
+    # n beyond the fused kernels (n <= 24, n d <= 60)
+    for fn in ("ff_cnf_generate", "ff_cnf_delta_logp"):
+        for nn, d in ((25, 2), (21, 3), (6, 4)):
+            refused(2, "fused CNF kernels serve n <= 24 particles with n*d <= 60 in d = 2, 3", fn, *flow[fn](r(net_ok), r(ode_ok), nn, d))
+    # --- entry points that only ask for a complete net (any width)
+    refused(1, "ff_radial_table_build: null pointer", "ff_radial_table_build", None, p8)
+    refused(1, "ff_radial_table_build: null pointer", "ff_radial_table_build", r(net_ok), None)
+    for net in bad_nets:
+        refused(1, "ff_radial_table_build: bad net", "ff_radial_table_build", r(net), p8)
+        refused(1, "ff_backflow_vjp: bad net", "ff_backflow_vjp", B, 6, 2, r(net), p8, p8, p8, p8)
+        refused(1, "ff_backflow_v_div: bad net", "ff_backflow_v_div", B, 6, 2, r(net), p8, p8, p8)
+        refused(1, "ff_backflow_v_div_f32: bad net", "ff_backflow_v_div_f32", B, 6, 2, r(net), p8, p8, p8)
+    refused(1, "ff_backflow_vjp: bad argument", "ff_backflow_vjp", B, 6, 2, None, p8, p8, p8, p8)
+    refused(2, "ff_backflow_vjp: n > 24 or d > 3", "ff_backflow_vjp", B, 25, 2, r(net_ok), p8, p8, p8, p8)
+    refused(1, "ff_backflow_v_div: bad argument", "ff_backflow_v_div", B, 6, 2, None, p8, p8, p8)
+    refused(2, "ff_backflow_v_div: n > 24 or d > 3", "ff_backflow_v_div", B, 6, 4, r(net_ok), p8, p8, p8)
+    refused(1, "ff_backflow_v_div_f32: bad argument", "ff_backflow_v_div_f32", B, 6, 2, None, p8, p8, p8)
+    refused(2, "ff_backflow_v_div_f32: n > 24 or d > 3", "ff_backflow_v_div_f32", B, 25, 2, r(net_ok), p8, p8, p8)
+    # --- (nup, ndn, tab_up, tab_dn): a spin species that has particles needs its orbital table (1); a determinant holds at most 12 (2)
+    spins = {      # arguments behind (stream, B, nup, ndn, tab_up, tab_dn)
+        "ff_eloc_nd": (("ff_eloc",) * 2, lambda: (None, r(net_ok), r(ode_ok), f64(2.0), 1) + (p8,) * 10 + (None,), (2,)),
+        "ff_eloc": (("ff_eloc",) * 2, lambda: (None, r(net_ok), r(ode_ok), f64(2.0), 1) + (p8,) * 10 + (None,), ()),
+        "ff_eloc_finish": (("ff_eloc_finish",) * 2, lambda: (None, f64(2.0), 1) + (p8,) * 10, ()),
+        "ff_eloc_finish3d": (("ff_eloc_finish3d: null orbital table", "ff_eloc_finish3d: walker too large"), lambda: (None, f64(2.0), 1) + (p8,) * 10, ()),
+        "ff_logprob": (("ff_logprob",) * 2, lambda: (None, p8, p8, p8, p8), ()),
+        "ff_logprob3d": (("ff_logprob3d: null pointer", "ff_logprob3d"), lambda: (None, p8, p8, p8, p8), ()),
+        "ff_mcmc_sample_noise3d": (("ff_mcmc_sample_noise3d",) * 2, lambda: (None, 10, f64(0.1), p8, p8, p8, p8, p8, p8), ()),
+        "ff_mcmc_sample3d": (("ff_mcmc_sample3d",) * 2, lambda: (None, 10, f64(0.1), C.c_uint64(1), i64(0), p8, p8, p8), ()),
+        "ff_mcmc_sample_noise": (("ff_mcmc: null pointer", "ff_mcmc"), lambda: (None, 10, f64(0.1), p8, p8, p8, p8, p8, p8), ()),
+        "ff_mcmc_sample": (("ff_mcmc: null pointer", "ff_mcmc"), lambda: (None, 10, f64(0.1), C.c_uint64(1), i64(0), p8, p8, p8), ()),
+        "ff_mcmc_continue": (("ff_mcmc: null pointer", "ff_mcmc"), lambda: (None, 10, f64(0.1), C.c_uint64(1), i64(0), p8, p8, p8, p8), ()),
+    }
+    for fn, ((null_tab, too_large), rest, dim) in spins.items():
+        null_tab = null_tab if ":" in null_tab else null_tab + ": null orbital table"
+        too_large = too_large if ":" in too_large else too_large + ": determinant larger than FF_MAX_NS"
+        for nup, ndn, tu, td in ((3, 3, None, p8), (3, 3, p8, None), (3, 0, None, None), (0, 3, p8, None)):
+            refused(1, null_tab, fn, B, nup, ndn, *dim, tu, td, *rest())
+        for nup, ndn in ((13, 3), (3, 13), (13, 0)):
+            refused(2, too_large, fn, B, nup, ndn, *dim, p8, p8, *rest())
+        assert getattr(lib, fn)(None, i64(0), 3, 0, *dim, p8, None, *rest()) == 0      # a species without particles needs no table
+    # where both are wrong: the sampler looks at the size first, everybody else at the tables
+    refused(2, "ff_mcmc: determinant larger than FF_MAX_NS", "ff_mcmc_sample", B, 13, 3, None, p8, *spins["ff_mcmc_sample"][1]())
+    refused(1, "ff_logprob: null orbital table", "ff_logprob", B, 13, 3, None, p8, *spins["ff_logprob"][1]())
+    refused(1, "ff_eloc: null orbital table", "ff_eloc", B, 13, 3, None, p8, *spins["ff_eloc"][1]())
+    refused(1, "ff_eloc: bad particle numbers or dimension", "ff_eloc_nd", B, 3, 3, 4, p8, p8, *spins["ff_eloc_nd"][1]())
+    refused(2, "ff_eloc_finish3d: walker too large", "ff_eloc_finish3d", B, 11, 11, p8, p8, *spins["ff_eloc_finish3d"][1]())      # 3 n > 64
