@@ -10,7 +10,7 @@ import time
 
 import torch
 
-from . import HO2D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, BetaVMC, checkpoint
+from . import HO2D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, BetaVMC, Observables, checkpoint
 from .utils import make_adam
 
 
@@ -33,6 +33,10 @@ def main(argv=None):
     parser.add_argument("--batch", type=int, default=8000, help="batch size (global, over all ranks)")
     parser.add_argument("--save", type=str, default=None, help="checkpoint file written after every iteration")
     parser.add_argument("--resume", type=str, default=None, help="checkpoint file to resume from")
+    parser.add_argument("--observe_out", type=str, default=None,
+                        help=".npz file for the radial densities and pair-distance distributions averaged over the run's iterations")
+    parser.add_argument("--observe_rmax", type=float, default=6.0, help="largest radius / distance of the observables' histograms")
+    parser.add_argument("--observe_bins", type=int, default=240, help="number of bins of the observables' histograms")
     args = parser.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -55,9 +59,11 @@ def main(argv=None):
                     CoulombPairPotential(args.Z), sp_potential=HO())
     model.to(device=device)
     optimizer = make_adam(model.parameters(), lr=1e-2)
+    if args.observe_out:
+        model.observables = Observables(args.nup, args.ndown, dim=2, rmax=args.observe_rmax, nbins=args.observe_bins, device=device)
     start_iter = 1
     if args.resume:
-        start_iter = checkpoint.load(args.resume, model, optimizer, device) + 1
+        start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None) + 1
     if rank == 0:
         print("beta = %.1f, nup = %d, ndown = %d, Z = %.1f" % (args.beta, args.nup, args.ndown, args.Z))
         print("deltaE = %.1f, total number of states = %d" % (args.deltaE, model.Nstates))
@@ -77,7 +83,11 @@ def main(argv=None):
                   "S:", model.S, "S_analytical:", model.S_analytical,
                   "Instant speed (hours per 100 iters):", speed)
             if args.save:
-                checkpoint.save(args.save, model, optimizer, i, device)
+                checkpoint.save(args.save, model, optimizer, i, device, observables=model.observables)
+    if args.observe_out:
+        model.observables.all_reduce_()
+        if rank == 0:
+            model.observables.save_npz(args.observe_out)
     if world > 1:
         torch.distributed.destroy_process_group()
 

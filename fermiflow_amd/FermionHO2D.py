@@ -14,7 +14,7 @@ import time
 
 import torch
 
-from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, checkpoint, native
+from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, Observables, checkpoint, native
 from .utils import make_adam
 
 
@@ -37,6 +37,10 @@ def main(argv=None):
                         help="precision of the sensitivity matrices of the local-energy pass from 11 particles on (not in the reference)")
     parser.add_argument("--save", type=str, default=None, help="checkpoint file written after every iteration")
     parser.add_argument("--resume", type=str, default=None, help="checkpoint file to resume from")
+    parser.add_argument("--observe_out", type=str, default=None,
+                        help=".npz file for the radial densities and pair-distance distributions averaged over the run's iterations")
+    parser.add_argument("--observe_rmax", type=float, default=6.0, help="largest radius / distance of the observables' histograms")
+    parser.add_argument("--observe_bins", type=int, default=240, help="number of bins of the observables' histograms")
     args = parser.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -63,9 +67,11 @@ def main(argv=None):
     model = GSVMC(args.nup, args.ndown, orbitals, basedist, cnf, CoulombPairPotential(args.Z), sp_potential=HO())
     model.to(device=device)
     optimizer = make_adam(model.parameters(), lr=1e-2)
+    if args.observe_out:
+        model.observables = Observables(args.nup, args.ndown, dim=args.dim, rmax=args.observe_rmax, nbins=args.observe_bins, device=device)
     start_iter = 1
     if args.resume:
-        start_iter = checkpoint.load(args.resume, model, optimizer, device) + 1
+        start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None) + 1
     if rank == 0:
         print("nup = %d, ndown = %d, Z = %.1f" % (args.nup, args.ndown, args.Z))
         print("batch = %d, iternum = %d." % (args.batch, args.iternum))
@@ -81,7 +87,11 @@ def main(argv=None):
         if rank == 0:
             print("iter: %03d" % i, "E:", model.E, "E_std:", model.E_std, "Instant speed (hours per 100 iters):", speed)
             if args.save:
-                checkpoint.save(args.save, model, optimizer, i, device)
+                checkpoint.save(args.save, model, optimizer, i, device, observables=model.observables)
+    if args.observe_out:
+        model.observables.all_reduce_()
+        if rank == 0:
+            model.observables.save_npz(args.observe_out)
     if world > 1:
         torch.distributed.destroy_process_group()
 

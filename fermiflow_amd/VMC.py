@@ -140,6 +140,8 @@ class _Sweep:
         # None, or a dict that receives per-stage torch.cuda.Event pairs + ODE stats.  {"stages": False}: only the event pair around the
         # local-energy pass and its statistics -- every stage marker is a hipEventRecord, ~8 us of pipeline bubble on this GPU
         self.profile = None
+        # None, or an observables.Observables: every sweep then adds its physical walkers to it (one launch right after the flow pass)
+        self.observables = None
         self.fast_backward = True    # _SweepScalar: `gradE.backward()` hands the gradient views to .grad without running the graph
         # ODE step-size warm start inside the sweep; FERMIFLOW_WARM_START=0 restores the cold start
         self.warm_start = os.environ.get("FERMIFLOW_WARM_START", "1") != "0"
@@ -240,6 +242,8 @@ class _Sweep:
                 hprev, uniform = self._h_flow, True
         x = native.cnf_generate(net, z, t0, t1, self.cnf.rtol, self.cnf.atol, walker_cost=cost,
                                 walker_h_init=hprev, walker_h_scale=0.75, walker_h_out=hg, walker_h_uniform=uniform)
+        if self.observables is not None:
+            self.observables.accumulate(x)
         self.walker_cost = cost          # the flow pass's cost class per walker (diagnostics and tests; ff_ode.walker_cost)
         hs = None
         if warm and not per_walker_h and self.adaptive_h:

@@ -1226,6 +1226,9 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
   }
 }
 
+// radial density and pair-distance histograms of the physical walkers (ff_observe_accumulate)
+#include "ff_observe.h"
+
 // =================================================================================================
 // C ABI
 // =================================================================================================
@@ -1802,6 +1805,37 @@ int ff_energy_finish(void* stream, const double* sums4, const double* shift_dev,
   FF_CHECK(sums4 && shift_dev && est3 && n_global > 0, FF_EINVAL, "ff_energy_finish: bad argument");
   FF_LAUNCH(ff_energy_finish_kernel, 1, FF_RBLOCK(64), stream, sums4, shift_dev, (double)n_global, est3);
   FF_LAUNCH_CHECK();
+  return FF_OK;
+}
+
+size_t ff_observe_buffer_bytes(int nbins) {
+  if (nbins < 1 || nbins > FF_OBS_MAX_BINS) return 0;
+  return sizeof(unsigned long long) * (3 + 3 * (size_t)FF_OBS_CLASSES * FF_OBS_SLOTS(nbins));
+}
+
+int ff_observe_accumulate(void* stream, int64_t B, int nup, int ndn, int d, const double* x, double rmax, int nbins, void* acc) {
+  FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && nup + ndn > 0 && d > 0 && acc && (x || B == 0), FF_EINVAL, "ff_observe: bad argument");
+  FF_CHECK(nbins >= 1, FF_EINVAL, "ff_observe: nbins < 1");
+  FF_CHECK(rmax > 0.0 && rmax <= 1.7976931348623157e308, FF_EINVAL, "ff_observe: rmax must be positive and finite");
+  FF_CHECK(nbins <= FF_OBS_MAX_BINS, FF_EUNSUPPORTED, "ff_observe: nbins > 1024");
+  FF_CHECK(d == 2 || d == 3, FF_EUNSUPPORTED, "ff_observe: d must be 2 or 3");
+  FF_CHECK(nup <= FF_MAX_N && ndn <= FF_MAX_N && nup + ndn <= FF_MAX_N && (nup + ndn) * d <= FF_OBS_MAX_COORD, FF_EUNSUPPORTED,
+           "ff_observe: n > 24 or n d > 60");
+  if (B == 0) return FF_OK;
+  const int n = nup + ndn, M = n * d, S = FF_OBS_CLASSES * FF_OBS_SLOTS(nbins);
+  int ncopy = FF_OBS_MAX_COPIES;
+  while (ncopy > 1 && S * ncopy > FF_OBS_HIST_WORDS) ncopy >>= 1;
+  const size_t hist_bytes = sizeof(double) * 2 * (size_t)((S * ncopy + 3) / 4), wave_bytes = sizeof(double) * FF_WAVE * (size_t)(M | 1);
+  int nwave = 4;
+  while (nwave > 1 && hist_bytes + nwave * wave_bytes > FF_OBS_LDS_BYTES) nwave >>= 1;
+  const unsigned magic = (unsigned)((((uint64_t)1 << 32) + (uint64_t)M - 1) / (uint64_t)M);
+  for (int64_t b0 = 0; b0 < B; b0 += FF_OBS_MAX_LAUNCH) {      // one launch up to 2^22 walkers; the last launch folds the call
+    const int64_t nb = B - b0 < FF_OBS_MAX_LAUNCH ? B - b0 : FF_OBS_MAX_LAUNCH;
+    const unsigned grid = ff_grid((nb + FF_WAVE - 1) / FF_WAVE, nwave, ff_device_cus() * FF_OBS_GRID_PER_CU);
+    FF_LAUNCH_LDS(ff_observe_kernel, grid, nwave * FF_WAVE, hist_bytes + nwave * wave_bytes, stream, nb, nup, n, d, x + b0 * M, rmax,
+                  (double)nbins / rmax, nbins, ncopy, magic, b0 + nb == B ? B : (int64_t)0, (unsigned long long*)acc);
+    FF_LAUNCH_CHECK();
+  }
   return FF_OK;
 }
 

@@ -349,6 +349,22 @@ size_t ff_energy_estimate_workspace_bytes(int64_t B);
 int ff_energy_estimate(void* stream, int64_t B, const double* e, const double* logp, const double* shift_dev, int64_t n_global,
                        double* sums4, double* est3, void* workspace);
 
+/* ---- observables: radial density and pair-distance histograms of walkers x (B, n, d), n = nup + ndn, the first nup particles spin-up.
+ * Classes c: 0 up and 1 down, r = |x_i|; 2 up-up, 3 up-down, 4 down-down, r = |x_i - x_j| over i < j.  A sample r = sqrt(sum_k delta_k^2)
+ * (fp64) goes to slot nbins + 1 ("invalid") if r is not finite, to slot nbins ("overflow") if r >= rmax, else to bin
+ * min((int)(r * (nbins / rmax)), nbins - 1) of its class: nbins + 2 slots per class.  A NaN coordinate spoils only the samples it is part of.
+ * acc: caller-owned, ff_observe_buffer_bytes(nbins) bytes of uint64 words, zeroed by the caller ONCE (and to reset), S = 5 (nbins + 2):
+ *   [0] calls | [1] walkers | sum[5][nbins + 2] | sumsq[5][nbins + 2] | scratch: S words and one ticket, zero between calls
+ * sum: total counts; sumsq: sum over calls of (that call's count)^2 -- one block per call for block standard errors.  Integers only, no
+ * floating-point atomics: the result does not depend on the grid, the order of the adds or how the walkers are spread over ranks
+ * (add sum, sumsq, calls and walkers of the ranks).  One launch per call on `stream` (one per 2^22 walkers of a larger B, still ONE call
+ * and one block); B = 0 is a no-op; the library allocates nothing.
+ * Limits: 1 <= nbins <= 1024, rmax > 0 finite, d in {2, 3}, n <= 24, n d <= 60.  Refusals (before any launch;
+ * ff_last_error() starts with "ff_observe:"): FF_EINVAL (1) for null pointers, nbins < 1, a bad rmax, negative sizes; FF_EUNSUPPORTED (2)
+ * for shapes beyond the limits.  ff_observe_buffer_bytes returns 0 for an nbins outside the limits. */
+size_t ff_observe_buffer_bytes(int nbins);
+int ff_observe_accumulate(void* stream, int64_t B, int nup, int ndn, int d, const double* x, double rmax, int nbins, void* acc);
+
 /* ---- three dimensions (groundwork for a 3-D trap; no upstream counterpart: src/orbitals.py:56 and src/base_dist.py:62
  * hard-code d = 2).  Orbital index k of HO3D: list order "for n in range(8) for nx in range(n+1) for ny in range(n+1-nx):
  * (nx, ny, n-nx-ny)", phi = pi^-3/4 exp(-r^2/2) h_nx(x) h_ny(y) h_nz(z), E = n + 3/2.  Walkers are (B, n, 3). -------------- */
