@@ -12,6 +12,7 @@
 #include "ff_common.h"
 #include "ff_slater.h"
 #include "ff_rng.h"
+#include "ff_mcmc.h"      // the proposal x + tau z in two roundings
 #include "ff_eloc_ws.h"
 
 #include "ff_slater_rows.h"
@@ -109,12 +110,8 @@ ff_logprob3d_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
   if (lap) lap[b] = lsum;
 }
 
-// two roundings, as torch evaluates x + tau * g (the backend must not contract them into one fma)
-FF_D double ff3_mul_rn(double a, double b) { double r = a * b; FF_OPAQUE(r); return r; }
-FF_D double ff3_add_rn(double a, double b) { double r = a + b; FF_OPAQUE(r); return r; }
-
 // FreeFermion.sample with SIXTEEN LANES PER DETERMINANT (two walkers x two spin species per wave), for every shape the
-// register-resident samplers of ff_walkers.hip do not cover: d = 3 (BASELINE configs[4]: two 10 x 10 determinants per step) and the
+// register-resident samplers of ff_mcmc.h do not cover: d = 3 (BASELINE configs[4]: two 10 x 10 determinants per step) and the
 // d = 2 systems beyond their template list.  Lane r of a group owns particle r of its species: it draws that particle's
 // proposal, evaluates its row of D_ij = phi_j(r_i), and the LU with partial pivoting runs without moving rows -- per column the
 // unused lane with the largest entry is the pivot (16-lane butterfly), publishes its row through LDS, the other unused lanes
@@ -173,7 +170,7 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
 
   // log|det| of the species' matrix at the positions xx (this lane's particle); identical on all lanes of the group.
   // Orbitals: the normalised Hermite functions of every coordinate once per call (three-term recurrence, as the register-resident
-  // samplers of ff_walkers.hip), phi_j = gauss * prod_c h_{deg_j,c}(x_c).  LU with partial pivoting without moving rows; the
+  // samplers of ff_mcmc.h), phi_j = gauss * prod_c h_{deg_j,c}(x_c).  LU with partial pivoting without moving rows; the
   // pivot of a column is found by ONE 32-bit maximum over the group's 16 lanes (DPP): key = |entry| rounded to float with the lane
   // index in the low four bits (equal keys: the lower lane) -- a pivot that is within 2^-19 of the largest entry instead of the
   // largest changes the rounding of log|det|, not its value.  A nonzero entry keys above every exact zero (entries below the float
@@ -346,8 +343,7 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
     int nacc = 0;
     for (int s = 0; s < steps; s++) {
       draw((uint32_t)(s + 1));
-#pragma unroll
-      for (int c = 0; c < D; c++) nx[c] = ff3_add_rn(x[c], ff3_mul_rn(tau, s_nrm[wk][i0 + c]));
+      ff_propose<D>(x, tau, &s_nrm[wk][i0], nx);
       const double uu = s_uu[wk];
       const double Rn = r2(nx), dRt = wsum(Rl - Rn);
       const double lhs = uu * exp(fmin(fmax(-dRt, -700.0), 708.0)) * PP2;
@@ -391,8 +387,7 @@ ff_mcmc_rows_kernel(int64_t B, int nup, int ndn, const int* __restrict__ tab_up,
       normals((uint32_t)(s + 1), z);
       uu = ff_uniform(seed, wid, (uint32_t)(s + 1), D == 2 ? (uint32_t)n : 0xffffu);
     }
-#pragma unroll
-    for (int c = 0; c < D; c++) nx[c] = ff3_add_rn(x[c], ff3_mul_rn(tau, z[c]));
+    ff_propose<D>(x, tau, z, nx);
     const double nl = logprob(nx);
     const double p = exp(nl - logp);
     const bool acc = uu < p;          // IEEE comparison: NaN rejects, +inf accepts (src/base_dist.py:67-68)

@@ -68,11 +68,12 @@ FF_D void ff_orbital(int k, double x, double y, double gauss /* pi^-1/2 exp(-r^2
 FF_D double ff_gauss2d(double x, double y) { return FF_PI_SQRT_INV * exp(-0.5 * (x * x + y * y)); }
 // same, with the in-house exp (argument clamped: exp(-708) is already a denormal-free 3e-308).  A NaN coordinate gives NaN, as
 // exp does: fmax would turn it into the clamp, and a NaN walker whose orbitals ignore that coordinate would get a finite row.
-FF_D double ff_gauss2d_fast(double x, double y) {
-  const double a = -0.5 * (x * x + y * y);
+FF_D double ff_gauss_of_r2(double r2) {
+  const double a = -0.5 * r2;
   const double gs = FF_PI_SQRT_INV * ff_exp(fmax(a, -708.0));
   return a == a ? gs : a;
 }
+FF_D double ff_gauss2d_fast(double x, double y) { return ff_gauss_of_r2(x * x + y * y); }
 
 // --------------------------------------------------------------------------------------------------
 // Register-resident log|det| for compile-time NS (MCMC hot loop).  The normalised Hermite function of degree n
@@ -285,7 +286,9 @@ FF_D double ff_slater_polydet_reg(const int* nx, const int* ny, const double* x,
 // one row of the Slater matrix: phi_j(x, y), j = 0..NS-1
 template <int NS>
 FF_D void ff_slater_row_reg(const int* nx, const int* ny, double x, double y, int md, double* row) {
-  double gs = ff_gauss2d_fast(x, y);
+  // r^2 with the fused product spelled out: left to -ffp-contract=fast, WHICH of x*x, y*y is fused into the sum depends on the code
+  // around the call, and log p of one walker would differ in its last bit between two sampler kernels (they are compared bit for bit)
+  double gs = ff_gauss_of_r2(fma(x, x, y * y));
 #pragma unroll
   for (int j = 0; j < NS; j++) row[j] = gs * ff_herm_rec(nx[j], x, md) * ff_herm_rec(ny[j], y, md);
 }

@@ -1,577 +1,19 @@
-// ff_walkers.hip -- one-lane-per-walker kernels: Metropolis sweep, Slater log-determinants and their
-// derivatives, potentials, stand-alone backflow/MLP evaluation, energy moments.
+// ff_walkers.hip -- one-lane-per-walker kernels: Slater log-determinants and their derivatives, potentials,
+// stand-alone backflow/MLP evaluation, energy moments; the entry points of the Metropolis samplers, whose
+// register-resident kernels are in ff_mcmc.h (sixteen lanes per determinant: ff_ho3d.hip).
 //
 // Data layout in HBM: walker coordinates (B, n, d) row-major fp64 exactly as the reference's tensors, so a
 // wave of 64 consecutive walkers reads one contiguous 64*n*d*8-byte span (fully used cache lines).
-// The Metropolis sweep keeps a walker's coordinates and log-probability in VGPRs for all `steps` proposals:
-// per walker-step the only HBM traffic is the proposal noise (parity mode) or nothing at all (Philox mode).
 #include <stdlib.h>
 #include "ff_common.h"
 #include "ff_slater.h"
 #include "ff_rng.h"
 
-#define FF_MAX_N 24  // particles per walker for the generic paths
+#define FF_MAX_N 24  // particles per walker for the generic one-lane-per-walker paths (backflow, potentials, observables)
 
-// x + tau*g exactly as torch computes it (two roundings): hipcc's default -ffp-contract=fast would fuse
-// the pair into one FMA and the walkers would no longer be bit-identical to the reference's.
-// the empty asm makes the product opaque, so the backend cannot contract mul+add into v_fma_f64
-FF_D double ff_mul_rn(double a, double b) { double r = a * b; FF_OPAQUE(r); return r; }
-FF_D double ff_add_rn(double a, double b) { double r = a + b; FF_OPAQUE(r); return r; }
-
-// ---------------------------------------------------------------------------------------------------
-// FreeFermion.sample (src/base_dist.py:58-71).  NU/ND > 0: compile-time spin sizes, everything in VGPRs.
-// NU = ND = -1: runtime sizes (private arrays).
-// ou/od: orbital indices (generic path) -- or, for compile-time sizes, ou = [nx | ny] degrees of the up
-// orbitals and od likewise for the down orbitals (decoded once, outside the step loop).
-template <int NU, int ND>
-FF_D double ff_logprob_value(int nup, int ndn, const int* ou, const int* od, const double* x, int md) {
-  double s = 0.0;
-  if constexpr (NU >= 0) {
-    if constexpr (NU > 0) s += ff_slater_logabsdet_reg<NU>(ou, ou + NU, x, md);
-    if constexpr (ND > 0) s += ff_slater_logabsdet_reg<ND>(od, od + ND, x + 2 * NU, md);
-  } else {
-    if (nup) s += ff_slater_general(nup, ou, x, nullptr, nullptr);
-    if (ndn) s += ff_slater_general(ndn, od, x + 2 * nup, nullptr, nullptr);
-  }
-  return 2.0 * s;
-}
-
-template <int NU, int ND, bool NOISE>
-__global__ void __launch_bounds__(128)
-ff_mcmc_kernel(int64_t B, int nup_rt, int ndn_rt, const int* __restrict__ tab_up, const int* __restrict__ tab_dn,
-               const int* __restrict__ wstate, int steps, double tau,
-               const double* __restrict__ g0, const double* __restrict__ g, const double* __restrict__ u,
-               uint64_t seed, int64_t woff,
-               double* __restrict__ x_out, double* __restrict__ logp_out, uint8_t* __restrict__ accept,
-               int* __restrict__ acc_count) {
-  constexpr bool FIXED = (NU >= 0);
-  const int nup = FIXED ? NU : nup_rt, ndn = FIXED ? ND : ndn_rt;
-  const int n = nup + ndn, M = 2 * n;
-  constexpr int MAXM = FIXED ? 2 * (NU + ND) : 2 * FF_MAX_N;
-  constexpr int MAXU = FIXED ? (NU > 0 ? NU : 1) : FF_MAX_NS, MAXD = FIXED ? (ND > 0 ? ND : 1) : FF_MAX_NS;
-  __shared__ int s_md;
-  int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (threadIdx.x == 0) s_md = 0;
-  __syncthreads();
-  const bool live = b < B;
-  if (!live) b = B - 1;          // idle tail lanes shadow the last walker (they take part in the barriers)
-  const int st = wstate ? wstate[b] : 0;
-  int ou[2 * MAXU], od[2 * MAXD];
-#pragma unroll
-  for (int j = 0; j < MAXU; j++) {
-    const int k = (j < nup) ? tab_up[st * nup + j] : 0;
-    if constexpr (FIXED) ff_orb_decode(k, ou[j], ou[MAXU + j]); else ou[j] = k;
-  }
-#pragma unroll
-  for (int j = 0; j < MAXD; j++) {
-    const int k = (j < ndn) ? tab_dn[st * ndn + j] : 0;
-    if constexpr (FIXED) ff_orb_decode(k, od[j], od[MAXD + j]); else od[j] = k;
-  }
-  // largest Hermite degree in the workgroup, as a scalar (wave-uniform loop bounds in ff_herm_rec)
-  int md = 0;
-  if constexpr (FIXED) {
-#pragma unroll
-    for (int j = 0; j < 2 * MAXU; j++) md = (j % MAXU < nup && ou[j] > md) ? ou[j] : md;
-#pragma unroll
-    for (int j = 0; j < 2 * MAXD; j++) md = (j % MAXD < ndn && od[j] > md) ? od[j] : md;
-    atomicMax(&s_md, md);
-    __syncthreads();
-    md = FF_UNIFORM(s_md);
-  }
-
-  double x[MAXM], nx[MAXM];
-  const uint64_t wid = (uint64_t)(woff + b);
-  if (NOISE || g0 != nullptr) {   // explicit initial walkers (parity mode; ff_mcmc_continue)
-#pragma unroll
-    for (int i = 0; i < MAXM; i++) if (i < M) x[i] = g0[b * M + i];
-  } else {
-#pragma unroll
-    for (int q = 0; q < (MAXM + 3) / 4; q++)
-      if (2 * q < n) {
-        double z4[4];
-        ff_normal_quad(seed, wid, 0u, (uint32_t)q, z4);
-#pragma unroll
-        for (int k = 0; k < 4; k++) if (4 * q + k < MAXM && 4 * q + k < M) x[4 * q + k] = z4[k];
-      }
-  }
-  double logp = ff_logprob_value<NU, ND>(nup, ndn, ou, od, x, md);
-  int nacc = 0;
-  // parity mode: the noise of step s+1 is requested from HBM before step s is computed (one step of software
-  // pipelining: a walker's chain is serial, so without it every step would expose a full HBM round trip)
-  double gq[MAXM], uq = 0.0;
-  if (NOISE && steps > 0) {
-#pragma unroll
-    for (int i = 0; i < MAXM; i++) if (i < M) gq[i] = g[b * M + i];
-    uq = u[b];
-  }
-  for (int s = 0; s < steps; s++) {
-    double ucur = 0.0;
-    if (NOISE) {
-#pragma unroll
-      for (int i = 0; i < MAXM; i++) if (i < M) nx[i] = ff_add_rn(x[i], ff_mul_rn(tau, gq[i]));
-      ucur = uq;
-      if (s + 1 < steps) {
-        const double* gs = g + ((int64_t)(s + 1) * B + b) * M;
-#pragma unroll
-        for (int i = 0; i < MAXM; i++) if (i < M) gq[i] = gs[i];
-        uq = u[(int64_t)(s + 1) * B + b];
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < (MAXM + 3) / 4; q++)
-        if (2 * q < n) {
-          double z4[4];
-          ff_normal_quad(seed, wid, (uint32_t)(s + 1), (uint32_t)q, z4);
-#pragma unroll
-          for (int k = 0; k < 4; k++)
-            if (4 * q + k < MAXM && 4 * q + k < M) nx[4 * q + k] = ff_add_rn(x[4 * q + k], ff_mul_rn(tau, z4[k]));
-        }
-    }
-    double nl = ff_logprob_value<NU, ND>(nup, ndn, ou, od, nx, md);
-    // p = exp(new_logp - logp) with torch's edge semantics: NaN stays NaN (rejects: a NaN walker, or -inf - -inf when a singular
-    // walker proposes another singular one), -inf gives exactly 0 (rejects), +inf (a walker with log p = -inf, e.g. every particle
-    // at the origin, proposing a regular one) accepts.  The clamped exponential gives e^708 for dlp >= 708, which every u < 1
-    // accepts, and 0 below -708, where torch's p is a denormal that only u == 0 exactly (a 2^-53 event) would accept.
-    const double dlp = nl - logp;
-    double p = exp(0.0);
-    if constexpr (FIXED) p = !(dlp == dlp) ? dlp : (dlp < -708.0 ? 0.0 : ff_exp(fmin(dlp, 708.0)));
-    else p = exp(dlp);
-    double uu = NOISE ? ucur : ff_uniform(seed, wid, (uint32_t)(s + 1), (uint32_t)n);
-    bool acc = uu < p;  // NaN p -> reject, +inf p -> accept (IEEE), as torch
-    if (acc) {
-#pragma unroll
-      for (int i = 0; i < MAXM; i++) if (i < M) x[i] = nx[i];
-      logp = nl;
-      nacc++;
-    }
-    if (accept && live) accept[(int64_t)s * B + b] = acc ? 1 : 0;
-  }
-  if (!live) return;
-#pragma unroll
-  for (int i = 0; i < MAXM; i++) if (i < M) x_out[b * M + i] = x[i];
-  if (logp_out) logp_out[b] = logp;
-  if (acc_count) acc_count[b] = nacc;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Metropolis chain with TWO lanes per walker, one per spin species (NU = ND = NS): at 65 536 walkers one lane per
-// walker is one wave per SIMD and nothing hides the latency of its serial chain (Philox rounds, Box-Muller, pivots).
-// Lane (b, spin) draws the proposals of its own particles, evaluates its own determinant; the two log|det| meet through
-// one DPP swap (a + b is commutative: both lanes form the identical sum, and it is the reference's 2*(up + down)), both
-// lanes take the same accept decision.  Same noise stream, same results, bit for bit, as ff_mcmc_kernel.
-template <int NS, bool NOISE>
-__global__ void __launch_bounds__(128)
-ff_mcmc_spin_kernel(int64_t B, const int* __restrict__ tab_up, const int* __restrict__ tab_dn, const int* __restrict__ wstate,
-                    int steps, double tau, const double* __restrict__ g0, const double* __restrict__ g,
-                    const double* __restrict__ u, uint64_t seed, int64_t woff, double* __restrict__ x_out,
-                    double* __restrict__ logp_out, uint8_t* __restrict__ accept, int* __restrict__ acc_count) {
-  constexpr int MS = 2 * NS, M = 2 * MS, n = 2 * NS;
-  // quads (Philox blocks of four normals, coordinates 4q..4q+3 of the walker) that cover one spin's coordinates
-  constexpr int NQ0 = (MS - 1) / 4 + 1, NQ1 = (2 * MS - 1) / 4 - MS / 4 + 1, NQ = NQ0 > NQ1 ? NQ0 : NQ1;
-  __shared__ int s_md;
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t b = gid >> 1;
-  const int sp = (int)(gid & 1), off = sp * MS;
-  if (threadIdx.x == 0) s_md = 0;
-  __syncthreads();
-  const bool live = b < B;
-  if (!live) b = B - 1;
-  const int st = wstate ? wstate[b] : 0;
-  const int* __restrict__ tab = sp ? tab_dn : tab_up;
-  int oo[2 * NS];
-#pragma unroll
-  for (int j = 0; j < NS; j++) ff_orb_decode(tab[st * NS + j], oo[j], oo[NS + j]);
-  int md = 0;
-#pragma unroll
-  for (int j = 0; j < 2 * NS; j++) md = oo[j] > md ? oo[j] : md;
-  atomicMax(&s_md, md);
-  __syncthreads();
-  md = FF_UNIFORM(s_md);
-
-  double x[MS], nx[MS];
-  const uint64_t wid = (uint64_t)(woff + b);
-  const int q0 = off >> 2;
-  auto draw = [&](uint32_t step, double* dst, bool propose) {   // this spin's normals of one step
-    double Z[NQ][4];
-#pragma unroll
-    for (int qq = 0; qq < NQ; qq++) ff_normal_quad(seed, wid, step, (uint32_t)(q0 + qq), Z[qq]);
-#pragma unroll
-    for (int i = 0; i < MS; i++) {
-      // coordinate off + i of the walker sits in quad (off + i) / 4; both spins' positions are compile-time constants
-      const double za = Z[i >> 2][i & 3], zb = Z[((MS + i) >> 2) - (MS >> 2)][(MS + i) & 3];
-      const double zv = (MS % 4 == 0) ? za : (sp ? zb : za);
-      dst[i] = propose ? ff_add_rn(x[i], ff_mul_rn(tau, zv)) : zv;
-    }
-  };
-  if (NOISE || g0 != nullptr) {   // explicit initial walkers (parity mode; ff_mcmc_continue)
-#pragma unroll
-    for (int i = 0; i < MS; i++) x[i] = g0[b * M + off + i];
-  } else {
-    draw(0u, x, false);
-  }
-  const double L0 = ff_slater_logabsdet_reg<NS>(oo, oo + NS, x, md);
-  double logp = 2.0 * (L0 + ff_swap1(L0));
-  int nacc = 0;
-  double gq[MS], uq = 0.0;
-  if (NOISE && steps > 0) {
-#pragma unroll
-    for (int i = 0; i < MS; i++) gq[i] = g[b * M + off + i];
-    uq = u[b];
-  }
-  for (int s = 0; s < steps; s++) {
-    double ucur = 0.0;
-    if (NOISE) {
-#pragma unroll
-      for (int i = 0; i < MS; i++) nx[i] = ff_add_rn(x[i], ff_mul_rn(tau, gq[i]));
-      ucur = uq;
-      if (s + 1 < steps) {
-        const double* gs = g + ((int64_t)(s + 1) * B + b) * M + off;
-#pragma unroll
-        for (int i = 0; i < MS; i++) gq[i] = gs[i];
-        uq = u[(int64_t)(s + 1) * B + b];
-      }
-    } else {
-      draw((uint32_t)(s + 1), nx, true);
-    }
-    const double L = ff_slater_logabsdet_reg<NS>(oo, oo + NS, nx, md);
-    const double nl = 2.0 * (L + ff_swap1(L));
-    const double dlp = nl - logp;
-    const double p = !(dlp == dlp) ? dlp : (dlp < -708.0 ? 0.0 : ff_exp(fmin(dlp, 708.0)));
-    const double uu = NOISE ? ucur : ff_uniform(seed, wid, (uint32_t)(s + 1), (uint32_t)n);
-    const bool acc = uu < p;
-    if (acc) {
-#pragma unroll
-      for (int i = 0; i < MS; i++) x[i] = nx[i];
-      logp = nl;
-      nacc++;
-    }
-    if (accept && live && sp == 0) accept[(int64_t)s * B + b] = acc ? 1 : 0;
-  }
-  if (!live) return;
-#pragma unroll
-  for (int i = 0; i < MS; i++) x_out[b * M + off + i] = x[i];
-  if (sp == 0) {
-    if (logp_out) logp_out[b] = logp;
-    if (acc_count) acc_count[b] = nacc;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// The Philox-fed chain of the two-lanes-per-walker layout above (throughput mode; the noise-fed template stays the reference's
-// arithmetic, operation for operation).  Same stream, same walkers as ff_rng_fill + ff_mcmc_spin_kernel<NS, true>
-// (test_mcmc_full_size_properties); what differs is how a step is evaluated (~925 wave-instructions per step):
-//  * the decision u < |psi(x')|^2 / |psi(x)|^2 (src/base_dist.py:66-68) is taken as
-//        u e^{R' - R} (P_up P_dn)^2 < (P'_up P'_dn)^2,   R = sum_i r_i^2,  P = det[h_nx_j(x_i) h_ny_j(y_i)]
-//    with P the determinant of the POLYNOMIAL parts of the orbitals (the Gaussians of a row factor out of the determinant):
-//    no exp per particle, no log per determinant, and the serial tail LU -> log -> exp -> compare of a step becomes
-//    determinant -> multiply -> compare -- the left side is formed while the determinant is;
-//  * determinants up to 3 x 3 in closed form (no pivot search, no reciprocal);
-//  * the walker's Philox blocks are dealt over its two lanes: lane 0 evaluates quads 0 .. mid, lane 1 the quads behind and the
-//    block of the uniform; for odd NS the second half of the middle quad and the uniform change lanes by one DPP swap
-//    (two blocks per lane and step at NS = 3 where every lane evaluated three);
-//  * step s + 1's normals are drawn while step s is decided (they depend on nothing of it).
-// log|psi|^2 of the final walker is evaluated once at the end by the same routine as everywhere else.
-template <int NS>
-__global__ void __launch_bounds__(128)
-ff_mcmc_spin_philox_kernel(int64_t B, const int* __restrict__ tab_up, const int* __restrict__ tab_dn, const int* __restrict__ wstate,
-                           int steps, double tau, const double* __restrict__ g0, uint64_t seed, int64_t woff,
-                           double* __restrict__ x_out, double* __restrict__ logp_out, int* __restrict__ acc_count) {
-  constexpr int MS = 2 * NS, M = 2 * MS, n = 2 * NS;
-  constexpr bool ODD = (NS & 1) != 0;
-  constexpr int MID = (NS - 1) / 2;                          // odd NS: the quad whose halves belong to different spins
-  constexpr int NB = ODD ? (NS + 1) / 2 : NS / 2 + 1;        // Philox blocks per lane and step
-  __shared__ int s_md;
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t b = gid >> 1;
-  const int sp = (int)(gid & 1), off = sp * MS;
-  if (threadIdx.x == 0) s_md = 0;
-  __syncthreads();
-  const bool live = b < B;
-  if (!live) b = B - 1;
-  const int st = wstate ? wstate[b] : 0;
-  const int* __restrict__ tab = sp ? tab_dn : tab_up;
-  int oo[2 * NS];
-#pragma unroll
-  for (int j = 0; j < NS; j++) ff_orb_decode(tab[st * NS + j], oo[j], oo[NS + j]);
-  int md = 0;
-#pragma unroll
-  for (int j = 0; j < 2 * NS; j++) md = oo[j] > md ? oo[j] : md;
-  atomicMax(&s_md, md);
-  __syncthreads();
-  md = FF_UNIFORM(s_md);
-
-  const uint64_t wid = (uint64_t)(woff + b);
-  auto swap32 = [](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); };
-  // this spin's normals of one step (z[i]: coordinate off + i of the walker) and the walker's uniform of that step
-  auto draw = [&](uint32_t step, double* z, double& u) {
-    ff_u4 R[NB];
-#pragma unroll
-    for (int k = 0; k < NB; k++) {
-      uint32_t slot;
-      if constexpr (ODD) slot = sp ? (uint32_t)(k < NB - 1 ? MID + 1 + k : n) : (uint32_t)k;
-      else slot = (k < NB - 1) ? (uint32_t)(sp * (NS / 2) + k) : (uint32_t)n;
-      R[k] = ff_philox(seed, wid, step, slot);
-    }
-    auto word = [&](int pair, int c) -> uint32_t {     // word c of pair `pair` of this lane's own blocks (static indices)
-      const ff_u4& r = R[pair >> 1];
-      return (pair & 1) ? (c ? r.w : r.z) : (c ? r.y : r.x);
-    };
-    uint32_t uh, ul;
-    if constexpr (ODD) {
-      const ff_u4& last = R[NB - 1];       // lane 0: the middle quad (its second half is lane 1's first pair); lane 1: the uniform's block
-      const uint32_t r0 = swap32(sp ? last.x : last.z), r1 = swap32(sp ? last.y : last.w);
-#pragma unroll
-      for (int j = 0; j < NS; j++) {
-        const uint32_t a0 = word(j, 0), a1 = word(j, 1);
-        const uint32_t b0 = j == 0 ? r0 : word(j > 0 ? j - 1 : 0, 0), b1 = j == 0 ? r1 : word(j > 0 ? j - 1 : 0, 1);
-        ff_normal_pair32(sp ? b0 : a0, sp ? b1 : a1, z[2 * j], z[2 * j + 1]);
-      }
-      uh = sp ? last.x : r0; ul = sp ? last.y : r1;
-    } else {
-#pragma unroll
-      for (int j = 0; j < NS; j++) ff_normal_pair32(word(j, 0), word(j, 1), z[2 * j], z[2 * j + 1]);
-      uh = R[NB - 1].x; ul = R[NB - 1].y;
-    }
-    u = ff_uniform_words(uh, ul);
-  };
-
-  double x[MS], zq[MS], uq = 0.0;
-  if (g0 != nullptr) {              // ff_mcmc_continue: explicit initial walkers
-#pragma unroll
-    for (int i = 0; i < MS; i++) x[i] = g0[b * M + off + i];
-  } else {
-    draw(0u, x, uq);
-  }
-  if (steps > 0) draw(1u, zq, uq);
-  double Rc = 0.0;
-#pragma unroll
-  for (int i = 0; i < MS; i++) Rc = fma(x[i], x[i], Rc);
-  double PP2;
-  {
-    const double P = ff_slater_polydet_reg<NS>(oo, oo + NS, x, md), PP = P * ff_swap1(P);
-    PP2 = PP * PP;
-  }
-  int nacc = 0;
-  for (int s = 0; s < steps; s++) {
-    double nx[MS];
-#pragma unroll
-    for (int i = 0; i < MS; i++) nx[i] = ff_add_rn(x[i], ff_mul_rn(tau, zq[i]));     // two roundings, as the noise-fed kernel
-    const double u = uq;
-    if (s + 1 < steps) draw((uint32_t)(s + 2), zq, uq);
-    double Rn = 0.0;
-#pragma unroll
-    for (int i = 0; i < MS; i++) Rn = fma(nx[i], nx[i], Rn);
-    const double dR = Rc - Rn, dRt = dR + ff_swap1(dR);
-    const double lhs = u * ff_exp(fmin(fmax(-dRt, -700.0), 708.0)) * PP2;
-    const double P = ff_slater_polydet_reg<NS>(oo, oo + NS, nx, md), PPn = P * ff_swap1(P), PPn2 = PPn * PPn;
-    // IEEE comparisons: a NaN on either side rejects; e^{R - R'} below the double range is the reference's p = 0 (reject)
-    const bool acc = (dRt >= -708.0) & (lhs < PPn2);
-    if (acc) {
-#pragma unroll
-      for (int i = 0; i < MS; i++) x[i] = nx[i];
-      Rc = Rn;
-      PP2 = PPn2;
-      nacc++;
-    }
-  }
-  const double L0 = ff_slater_logabsdet_reg<NS>(oo, oo + NS, x, md);
-  const double logp = 2.0 * (L0 + ff_swap1(L0));
-  if (!live) return;
-#pragma unroll
-  for (int i = 0; i < MS; i++) x_out[b * M + off + i] = x[i];
-  if (sp == 0) {
-    if (logp_out) logp_out[b] = logp;
-    if (acc_count) acc_count[b] = nacc;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------
-// Metropolis chain of ONE spin species (ndown = 0: the finite-temperature runs, src/BetaFermionHO2D.py) with TWO lanes per
-// walker.  One lane per walker is one wave per SIMD at 65 536 walkers and nothing hides its serial chain; there is no second
-// species to split off here, so the lanes split the PARTICLES: lane h of a walker owns the Philox quads q = h, h + 2, ...
-// (quad q = the four normals of particles 2q, 2q + 1), proposes those particles' moves and evaluates their rows of the Slater
-// matrix; the rows change hands through one DPP swap per entry, then both lanes run the same LU on the same matrix -- the
-// same determinant bits, hence the same accept decision, as ff_mcmc_kernel.  Same noise stream, same results, bit for bit.
-template <int NS, bool NOISE>
-__global__ void __launch_bounds__(128)
-ff_mcmc_pair_kernel(int64_t B, const int* __restrict__ tab_up, const int* __restrict__ wstate, int steps, double tau,
-                    const double* __restrict__ g0, const double* __restrict__ g, const double* __restrict__ u, uint64_t seed,
-                    int64_t woff, double* __restrict__ x_out, double* __restrict__ logp_out, uint8_t* __restrict__ accept,
-                    int* __restrict__ acc_count) {
-  constexpr int M = 2 * NS, NQT = (NS + 1) / 2, NQL = (NQT + 1) / 2, NPL = 2 * NQL, MPL = 2 * NPL;   // quads total / per lane, slots
-  __shared__ int s_md;
-  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int64_t b = gid >> 1;
-  const int h = (int)(gid & 1);
-  if (threadIdx.x == 0) s_md = 0;
-  __syncthreads();
-  const bool live = b < B;
-  if (!live) b = B - 1;
-  const int st = wstate ? wstate[b] : 0;
-  int oo[2 * NS];
-#pragma unroll
-  for (int j = 0; j < NS; j++) ff_orb_decode(tab_up[st * NS + j], oo[j], oo[NS + j]);
-  int md = 0;
-#pragma unroll
-  for (int j = 0; j < 2 * NS; j++) md = oo[j] > md ? oo[j] : md;
-  atomicMax(&s_md, md);
-  __syncthreads();
-  md = FF_UNIFORM(s_md);
-
-  // slot s of this lane: particle pid(s) = 4 (s / 2) + 2 h + (s & 1)  (quad q = 2 (s / 2) + h); it exists if pid < NS
-  double xm[MPL], nxm[MPL];
-#pragma unroll
-  for (int i = 0; i < MPL; i++) xm[i] = 0.0;
-  const uint64_t wid = (uint64_t)(woff + b);
-  auto pid = [&](int sl) -> int { return 4 * (sl >> 1) + 2 * h + (sl & 1); };
-  auto draw = [&](uint32_t step, double* dst, bool propose) {
-#pragma unroll
-    for (int k = 0; k < NQL; k++) {
-      double z4[4];
-      ff_normal_quad(seed, wid, step, (uint32_t)(2 * k + h), z4);
-#pragma unroll
-      for (int c = 0; c < 4; c++) dst[4 * k + c] = propose ? ff_add_rn(xm[4 * k + c], ff_mul_rn(tau, z4[c])) : z4[c];
-    }
-  };
-  auto load = [&](const double* src, double* dst) {     // this lane's coordinates of a (B, NS, 2) array row
-#pragma unroll
-    for (int sl = 0; sl < NPL; sl++) {
-      const int p = pid(sl) < NS ? pid(sl) : 0;
-      dst[2 * sl] = src[2 * p]; dst[2 * sl + 1] = src[2 * p + 1];
-    }
-  };
-  // log|psi|^2 of the walker whose coordinates (this lane's share) are in `xs`
-  auto logprob = [&](const double* xs) -> double {
-    double Dm[NPL][NS];
-#pragma unroll
-    for (int sl = 0; sl < NPL; sl++) ff_slater_row_reg<NS>(oo, oo + NS, xs[2 * sl], xs[2 * sl + 1], md, Dm[sl]);
-    double Dfull[NS][NS];
-#pragma unroll
-    for (int i = 0; i < NS; i++) {
-      const int q = i >> 1, owner = q & 1, sl = 2 * (q >> 1) + (i & 1);   // static: which lane and slot hold row i
-#pragma unroll
-      for (int j = 0; j < NS; j++) {
-        const double mine = Dm[sl][j], other = ff_swap1(mine);
-        Dfull[i][j] = (h == owner) ? mine : other;
-      }
-    }
-    return 2.0 * (0.0 + ff_lu_logabsdet_reg<NS>(Dfull));
-  };
-  // determinant (up to its sign) of the polynomial parts of the orbitals, same exchange of rows
-  auto polydet = [&](const double* xs) -> double {
-    double Dm[NPL][NS];
-#pragma unroll
-    for (int sl = 0; sl < NPL; sl++) ff_poly_row_reg<NS>(oo, oo + NS, xs[2 * sl], xs[2 * sl + 1], md, Dm[sl]);
-    double Dfull[NS][NS];
-#pragma unroll
-    for (int i = 0; i < NS; i++) {
-      const int q = i >> 1, owner = q & 1, sl = 2 * (q >> 1) + (i & 1);
-#pragma unroll
-      for (int j = 0; j < NS; j++) {
-        const double mine = Dm[sl][j], other = ff_swap1(mine);
-        Dfull[i][j] = (h == owner) ? mine : other;
-      }
-    }
-    return ff_det_reg<NS>(Dfull);
-  };
-
-  if (NOISE || g0 != nullptr) load(g0 + b * M, xm);
-  else draw(0u, xm, false);
-  int nacc = 0;
-  double logp;
-  if constexpr (NOISE) {
-    logp = logprob(xm);
-    double gq[MPL], uq = 0.0;
-    if (steps > 0) { load(g + b * M, gq); uq = u[b]; }
-    for (int s = 0; s < steps; s++) {
-      double ucur = 0.0;
-#pragma unroll
-      for (int i = 0; i < MPL; i++) nxm[i] = ff_add_rn(xm[i], ff_mul_rn(tau, gq[i]));
-      ucur = uq;
-      if (s + 1 < steps) { load(g + ((int64_t)(s + 1) * B + b) * M, gq); uq = u[(int64_t)(s + 1) * B + b]; }
-      const double nl = logprob(nxm);
-      const double dlp = nl - logp;
-      const double p = !(dlp == dlp) ? dlp : (dlp < -708.0 ? 0.0 : ff_exp(fmin(dlp, 708.0)));
-      const double uu = ucur;
-      const bool acc = uu < p;
-      if (acc) {
-#pragma unroll
-        for (int i = 0; i < MPL; i++) xm[i] = nxm[i];
-        logp = nl;
-        nacc++;
-      }
-      if (accept && live && h == 0) accept[(int64_t)s * B + b] = acc ? 1 : 0;
-    }
-  } else {
-    // Philox-fed chain: the decision as u e^{R' - R} P^2 < P'^2 on the determinant of the polynomial parts (see
-    // ff_mcmc_spin_philox_kernel); the walkers are those of the branch above on the materialised stream
-    auto r2sum = [&](const double* xs) -> double {       // this lane's share of sum_i r_i^2 (absent particles: none)
-      double r = 0.0;
-#pragma unroll
-      for (int sl = 0; sl < NPL; sl++) { const double t = fma(xs[2 * sl], xs[2 * sl], xs[2 * sl + 1] * xs[2 * sl + 1]); r += (pid(sl) < NS) ? t : 0.0; }
-      return r;
-    };
-    double Rc = r2sum(xm);
-    double P2 = polydet(xm);
-    P2 *= P2;
-    double uq = 0.0;
-    if (steps > 0) { draw(1u, nxm, false); uq = ff_uniform(seed, wid, 1u, (uint32_t)NS); }
-    for (int s = 0; s < steps; s++) {
-      double cur[MPL];
-#pragma unroll
-      for (int i = 0; i < MPL; i++) cur[i] = ff_add_rn(xm[i], ff_mul_rn(tau, nxm[i]));
-      const double uu = uq;
-      // step s + 1's normals and uniform: they depend on nothing of this step
-      if (s + 1 < steps) { draw((uint32_t)(s + 2), nxm, false); uq = ff_uniform(seed, wid, (uint32_t)(s + 2), (uint32_t)NS); }
-      const double Rn = r2sum(cur), dR = Rc - Rn, dRt = dR + ff_swap1(dR);
-      const double lhs = uu * ff_exp(fmin(fmax(-dRt, -700.0), 708.0)) * P2;
-      double Pn2 = polydet(cur);
-      Pn2 *= Pn2;
-      const bool acc = (dRt >= -708.0) & (lhs < Pn2);
-      if (acc) {
-#pragma unroll
-        for (int i = 0; i < MPL; i++) xm[i] = cur[i];
-        Rc = Rn;
-        P2 = Pn2;
-        nacc++;
-      }
-    }
-    logp = logprob(xm);
-  }
-  if (!live) return;
-#pragma unroll
-  for (int sl = 0; sl < NPL; sl++) {
-    if (pid(sl) < NS) { x_out[b * M + 2 * pid(sl)] = xm[2 * sl]; x_out[b * M + 2 * pid(sl) + 1] = xm[2 * sl + 1]; }
-  }
-  if (h == 0) {
-    if (logp_out) logp_out[b] = logp;
-    if (acc_count) acc_count[b] = nacc;
-  }
-}
-
-// materialise the Philox noise stream of ff_mcmc_kernel<.., false>
-__global__ void __launch_bounds__(128)
-ff_rng_fill_kernel(int64_t B, int n, int steps, uint64_t seed, int64_t woff, double* __restrict__ g0,
-                   double* __restrict__ g, double* __restrict__ u) {
-  int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const int M = 2 * n;
-  const uint64_t wid = (uint64_t)(woff + b);
-  for (int q = 0; 2 * q < n; q++) {
-    double z4[4];
-    ff_normal_quad(seed, wid, 0u, (uint32_t)q, z4);
-    for (int k = 0; k < 4; k++) if (4 * q + k < M) g0[b * M + 4 * q + k] = z4[k];
-  }
-  for (int s = 0; s < steps; s++) {
-    double* gs = g + ((int64_t)s * B + b) * M;
-    for (int q = 0; 2 * q < n; q++) {
-      double z4[4];
-      ff_normal_quad(seed, wid, (uint32_t)(s + 1), (uint32_t)q, z4);
-      for (int k = 0; k < 4; k++) if (4 * q + k < M) gs[4 * q + k] = z4[k];
-    }
-    u[(int64_t)s * B + b] = ff_uniform(seed, wid, (uint32_t)(s + 1), (uint32_t)n);
-  }
-}
+// the register-resident Metropolis samplers and ff_rng_fill_kernel
+#define FF_MCMC_BUILD_KERNELS
+#include "ff_mcmc.h"
 
 // ---------------------------------------------------------------------------------------------------
 // LogAbsSlaterDet forward / backward (src/slater.py:13-62), one lane per walker
@@ -1247,9 +689,7 @@ static void launch_mcmc(bool noise, void* stream, int64_t B, int nup, int ndn, c
     else
       FF_LAUNCH((ff_mcmc_spin_philox_kernel<NU>), ff_grid(2 * B, 128), 128, stream, B, tu, td, ws, steps, tau, g0, seed, woff,
                 x_out, logp_out, acc_count);
-    return;
-  }
-  if constexpr (ND == 0 && NU >= 2 && NU <= 6) {
+  } else if constexpr (ND == 0 && NU >= 2 && NU <= 6) {
     // one spin species: two lanes per walker split the particles (ff_mcmc_pair_kernel)
     if (noise)
       FF_LAUNCH((ff_mcmc_pair_kernel<NU, true>), ff_grid(2 * B, 128), 128, stream, B, tu, ws, steps, tau, g0, g, u, seed, woff, x_out,
@@ -1257,14 +697,15 @@ static void launch_mcmc(bool noise, void* stream, int64_t B, int nup, int ndn, c
     else
       FF_LAUNCH((ff_mcmc_pair_kernel<NU, false>), ff_grid(2 * B, 128), 128, stream, B, tu, ws, steps, tau, g0, g, u, seed, woff, x_out,
                 logp_out, accept, acc_count);
-    return;
+  } else {
+    // one lane per walker: (1, 0) and (10, 0)
+    if (noise)
+      FF_LAUNCH((ff_mcmc_kernel<NU, ND, true>), ff_grid(B, 128), 128, stream, B, nup, ndn, tu, td, ws, steps, tau, g0, g, u, seed, woff,
+                x_out, logp_out, accept, acc_count);
+    else
+      FF_LAUNCH((ff_mcmc_kernel<NU, ND, false>), ff_grid(B, 128), 128, stream, B, nup, ndn, tu, td, ws, steps, tau, g0, g, u, seed, woff,
+                x_out, logp_out, accept, acc_count);
   }
-  if (noise)
-    FF_LAUNCH((ff_mcmc_kernel<NU, ND, true>), ff_grid(B, 128), 128, stream, B, nup, ndn, tu, td, ws, steps, tau, g0, g, u, seed, woff,
-              x_out, logp_out, accept, acc_count);
-  else
-    FF_LAUNCH((ff_mcmc_kernel<NU, ND, false>), ff_grid(B, 128), 128, stream, B, nup, ndn, tu, td, ws, steps, tau, g0, g, u, seed, woff,
-              x_out, logp_out, accept, acc_count);
 }
 
 extern int ff_mcmc_rows_launch(void* stream, int d, bool noise, int64_t B, int nup, int ndn, const int* tu, const int* td, const int* ws,

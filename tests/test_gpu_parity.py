@@ -184,6 +184,33 @@ def test_sixteen_lane_sampler_philox_equals_noise_path(dev, nup, ndn):
     assert (ao == N(a1[:, rows])).all() and (xo == N(x2[rows])).all()
 
 
+FF_MC_SHAPES = [(1, 0), (2, 0), (3, 0), (4, 0), (5, 0), (6, 0), (10, 0), (1, 1), (2, 2), (3, 3), (4, 4), (5, 5), (6, 6)]
+
+
+@pytest.mark.parametrize("nup,ndn", FF_MC_SHAPES)
+def test_register_resident_samplers_philox_equals_noise_path(dev, nup, ndn):
+    """Every shape of the register-resident template list (csrc/ff_mcmc.h): the Philox-fed chain, the chain continued from the
+    stream's own initial walkers and the noise-fed chain on the materialised stream are one chain -- walkers and log p bit for
+    bit, accept counts == the column sums of the accept mask -- and the noise-fed chain is the oracle's.  Covers the even-NS and
+    NS = 1, 5 dealing of Philox blocks of the one-lane-per-spin kernel and the (1, 0) one-lane kernel.  193 walkers: with two lanes
+    per walker three full workgroups and one with a single live walker and 126 shadow lanes; with one lane per walker a ragged one."""
+    from fermiflow_amd import native
+    B, S, n = 193, 12, nup + ndn
+    tu = native.orbital_table(list(range(nup)), dev)
+    td = native.orbital_table(list(range(ndn)), dev) if ndn else None
+    g0, g, u = native.rng_fill(B, n, S, 20261, dev, walker_offset=7)
+    x1, lp1, a1 = native.mcmc_sample_noise(tu, td, nup, ndn, g0, g, u, 0.1)
+    x2, lp2, c2 = native.mcmc_sample(tu, td, nup, ndn, B, S, 0.1, 20261, dev, walker_offset=7)
+    x3, lp3, c3 = native.mcmc_continue(tu, td, nup, ndn, g0, S, 0.1, 20261, walker_offset=7)
+    cnt = a1.sum(0).to(torch.int32)
+    assert torch.equal(x1, x2) and torch.equal(x1, x3)
+    assert torch.equal(lp1, lp2) and torch.equal(lp1, lp3)
+    assert torch.equal(cnt, c2.to(torch.int32)) and torch.equal(cnt, c3.to(torch.int32))
+    xo, lo, ao = O.mcmc_noise(N(g0), N(g), N(u), nup, ndn)
+    assert (N(x1) == xo).all() and (N(a1) == ao).all()
+    np.testing.assert_allclose(N(lp1), lo, rtol=1e-12, atol=1e-12)
+
+
 def test_philox_stream_is_normal_and_symmetric(dev):
     """csrc/ff_rng.h: the proposal normals are Box-Muller on 32-bit Philox words evaluated with the hardware fp32
     transcendentals (v_log_f32, v_sqrt_f32, v_sin_f32, v_cos_f32) and promoted to fp64; each normal takes its sign from a bit of

@@ -10,9 +10,9 @@ make_golden.py edges from the reference itself, and tests/common.py):
   * coincident same-spin particles (identical rows): the determinant is exactly 0, log p = -inf, as in the oracle and in exact
     arithmetic.  The reference returns a finite value there that depends on LAPACK's rounding; that is a deliberate deviation
     ("Behavioural differences"), not a tolerance.
-Families: ff_mcmc_kernel (register-resident one lane per walker: (10, 0)), ff_mcmc_spin_kernel / ff_mcmc_spin_philox_kernel (nup =
-ndn), ff_mcmc_pair_kernel (ndn = 0), ff_mcmc_rows_kernel (sixteen lanes: (2, 1), (4, 3), (7, 6), (0, 7) and d = 3).  The runtime-size
-ff_mcmc_kernel is not instantiated by any entry point (shapes outside the template list go to the sixteen-lane kernel).
+Families (csrc/ff_mcmc.h): ff_mcmc_kernel (register-resident one lane per walker: (10, 0)), ff_mcmc_spin_kernel /
+ff_mcmc_spin_philox_kernel (nup = ndn), ff_mcmc_pair_kernel (ndn = 0); csrc/ff_ho3d.hip: ff_mcmc_rows_kernel (sixteen lanes: (2, 1),
+(4, 3), (7, 6), (0, 7) and d = 3).  ff_mcmc_kernel has compile-time sizes only; shapes outside the template list go to the sixteen-lane kernel.
 """
 import numpy as np
 import pytest

@@ -78,6 +78,25 @@ def test_particle_split_metropolis_kernel(nup):
     assert (x1 == x2).all() and (acc1.sum(0) == cnt).all()
 
 
+@pytest.mark.parametrize("nup,ndn", [(1, 0), (2, 0), (3, 0), (4, 0), (5, 0), (6, 0), (10, 0), (1, 1), (2, 2), (3, 3), (4, 4), (5, 5), (6, 6)])
+def test_register_resident_samplers_philox_equals_noise_path(nup, ndn):
+    """Every shape of the register-resident template list (csrc/ff_mcmc.h): the Philox-fed chain, the chain continued from the
+    stream's own initial walkers and the noise-fed chain on the materialised stream are one chain -- walkers and log p bit for
+    bit, accept counts == the column sums of the accept mask -- and the noise-fed chain is the oracle's.  67 walkers: with two
+    lanes per walker one full workgroup and one with three live walkers; with one lane per walker a ragged workgroup."""
+    B, steps, n = 67, 6, nup + ndn
+    g0, g, u = S.rng_fill(B, n, steps, 20261, offset=7)
+    x1, lp1, a1 = S.mcmc_noise(g0, g, u, nup, ndn)
+    x2, lp2, c2 = S.mcmc(B, nup, ndn, steps, 20261, offset=7)
+    x3, lp3, c3 = S.mcmc_continue(g0, nup, ndn, steps, 20261, offset=7)
+    assert np.array_equal(x1, x2) and np.array_equal(x1, x3)
+    assert np.array_equal(lp1, lp2) and np.array_equal(lp1, lp3)
+    assert np.array_equal(a1.sum(0), c2) and np.array_equal(a1.sum(0), c3)
+    xo, lo, ao = O.mcmc_noise(g0, g, u, nup, ndn)
+    assert (x1 == xo).all() and (a1 == ao).all()
+    np.testing.assert_allclose(lp1, lo, rtol=1e-12, atol=1e-12)
+
+
 def test_backflow_kernel(golden):
     G = golden["g3_backflow"]
     for k in (1, 2, 3):
