@@ -184,13 +184,9 @@ class _Sweep:
         # (a rejected first step costs the whole wave two more attempts, and at a rate p that is 1 - (1 - p)^G of the waves):
         # 1 - 0.65^(1/G) within [0.06, 0.25] -- 0.10 at the matrix-core kernel's four (measured on settled tables, tools/probes/
         # table_settle.py: trained flow 24.4 -> 23.9 evaluations per walker against 0.20, driver-1000 32.5 -> 31.2), 0.25 for the
-        # one-walker-per-workgroup kernels (configs[4]: 0.10 costs 3.4 % more evaluations than 0.20 there).  Kernels by shape: csrc/
-        # ff_cnf_fwd.hip dispatch_fwd (column sweep up to 3 particles: 64 / (n d) walkers per wave; matrix-core kernel 4-6: four; row
-        # layout 7-8: two; one walker per wave beyond, and from 5 particles in d = 3).
-        if dim == 2:
-            G = min(16, 64 // (2 * n)) if n <= 3 else (4 if n <= 6 else (2 if n <= 8 else 1))
-        else:
-            G = max(1, 64 // (3 * n)) if n <= 4 else 1
+        # one-walker-per-workgroup kernels (configs[4]: 0.10 costs 3.4 % more evaluations than 0.20 there).  G by shape: the library's
+        # own plan (csrc/ff_plan.h; DESIGN.md has the table).
+        G = native.kernel_plan("eloc", n, dim)[1]
         self._h_shrink_at = min(0.25, max(0.06, 1.0 - 0.65 ** (1.0 / G)))
         self._h_tab = None           # [2, 32] device table (double-buffered), row _h_tab_cur is current
         self._h_tab_cur = 0

@@ -1,6 +1,7 @@
 // ff_api.hip -- library-wide pieces of the C ABI (version, error string) and the host-side set-up code that the
 // reference keeps in Python: enumeration of the low-lying many-body states (src/orbitals.py:14-54).
 #include "ff_host.h"
+#include "ff_plan.h"
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -59,6 +60,17 @@ std::vector<Subset> subsets(const double* price, int n, int k, double pmax) {
 extern "C" {
 int ff_version(void) { return 109; }   // 109: ff_walker_schedule takes shrink_at (no struct change); 108: ff_ode gained walker_h_equal; 107: ff_scale_counts takes the interval and fills 128 counts, ff_walker_schedule reads as many (no struct change); 106: ff_ode gained after_main_event; 105: ff_walker_schedule, ff_rng_fill3d (no struct change); 104: ff_ode gained compact_finish; 103: ff_ode gained heavy_class / heavy_tol / sum_weight (102: walker_class / sens_tol / walker_h_scale_loose / sens_tol_class)
 const char* ff_last_error(void) { return g_ff_err; }
+
+int ff_kernel_plan(int call, int n, int d, int64_t cus, ff_kernel_plan_info* out) {
+  FF_CHECK(call >= FF_CALL_FLOW && call <= FF_CALL_ADJOINT_FALLBACK && cus >= 1 && out, FF_EINVAL, "ff_kernel_plan: bad argument");
+  const bool fallback = call == FF_CALL_FLOW_FALLBACK || call == FF_CALL_ELOC_FALLBACK || call == FF_CALL_ADJOINT_FALLBACK;
+  const bool eloc = call == FF_CALL_ELOC || call == FF_CALL_ELOC_FALLBACK;      // the one call that launches on a work queue
+  const ff_plan p = eloc ? ff_plan_eloc(n, d, fallback) : (call <= FF_CALL_FLOW_FALLBACK ? ff_plan_flow(n, d, fallback) : ff_plan_adjoint(n, d, fallback));
+  FF_CHECK(p.family != FF_FAMILY_NONE, FF_EUNSUPPORTED, "fused CNF kernels serve n <= 24 particles with n*d <= 60 in d = 2, 3");
+  const int64_t cap = p.cap(cus, eloc);
+  *out = {p.family, p.group, cap >= FF_GRID_CAP ? 0 : cap * p.wg_walkers()};
+  return FF_OK;
+}
 
 // Orbitals.fermion_states (src/orbitals.py:33-54), host code, no GPU involved.  See include/fermiflow.h.
 int64_t ff_fermion_states(int n_orb, const double* orb_E, int nup, int ndn, double deltaE, int64_t capacity,

@@ -209,34 +209,8 @@ FF_D void ff_deposit5(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict
 #ifndef FF_ADJ_WPS
 #define FF_ADJ_WPS 1     // waves per SIMD the tabulated adjoint is compiled for (A/B knob: tools/probes/adj_ab.py)
 #endif
-#ifndef FF_ADJ_WPW
-#define FF_ADJ_WPW 2     // waves per workgroup of the tabulated adjoint (1: the single-wave workgroups of rounds 1-3)
-#endif
-// Walkers per wave of the tabulated adjoint.  The forward kernels pack 64 / M walkers into a wave; here every lane also
-// carries the six stage records of its radii, and at 6 particles (5 walkers x 21 radii = 105 radii: two per lane) that
-// put the kernel at 360 registers.  With THREE walkers (63 radii: one per lane) it takes 292 and is exactly as fast
-// (0.67 ms per 65 536 walkers either way: the radius phase is what a wave-evaluation waits for) -- and 292 + 164 <= 512:
-// a wave of the Metropolis kernel now fits the same SIMD, so the next sweep's walkers are sampled BESIDE the adjoint
-// (GSVMC prefetch, DESIGN.md 6: 1.11 -> 0.78 ms for the two together; tools/probes/overlap.py).
-#ifndef FF_ADJ_G12
-#define FF_ADJ_G12 3
-#endif
-// (4, 5, 7, 9, 10 and 11 particles likewise -- round 6: with 64 / M walkers their 80-165 radii per wave took two or three record slots
-// per lane, 144-556 B of scratch at two waves per SIMD where the allocator had no AGPRs left; as many walkers as keep the radii at one
-// per lane -- at least one walker -- instead)
-constexpr int ff_adjtab_G(int n, int d) {
-  const int M = n * d;
-  if (M <= 0 || M > FF_WAVE) return 0;
-  const int g = FF_WAVE / M > 16 ? 16 : FF_WAVE / M;
-  if (M == 12) return FF_ADJ_G12;
-  if (d == 2 && (n == 4 || n == 5 || n == 7 || n == 9 || n == 10 || n == 11)) {      // (measured: 8 and 12 particles are faster at 64 / M)
-    const int gr = FF_WAVE / (n * (n + 1) / 2);
-    return gr < 1 ? 1 : (gr < g ? gr : g);
-  }
-  return g;
-}
+// (FF_ADJ_WPW waves per workgroup, ff_adjtab_G walkers per wave: ff_plan.h)
 template <int N, int D> struct ff_adjtab_geom { static constexpr int G = ff_adjtab_G(N, D); };
-static int adj_tab_G(int n, int d) { return ff_adjtab_G(n, d); }
 
 // WPW waves per workgroup.  A wave at 290 registers and 33 KB of LDS (27 KB of it the deposit table) is alone on its SIMD, and
 // every phase of its right-hand side -- radial-table fetch, LDS round trips, dependent fp64 issue -- is exposed: 5 100 cycles per
@@ -654,7 +628,6 @@ ff_ode_adjtab_kernel(ff_adj_args A) {
 }
 
 extern bool ff_wide_forced();                  // ff_wide.hip
-extern int ff_wide_supported(int n, int d);
 #include "ff_adj_wide.h"   // one walker per wave, run-time particle number (n > 12 in d = 2, n > 4 in d = 3)
 
 // Wtot[t][j < NLDS][k] = sum over workgroups of their private tables; j >= NLDS was added in place.
@@ -794,16 +767,14 @@ __global__ void __launch_bounds__(256) ff_zero_kernel(double* __restrict__ p, si
 #include "ff_host.h"
 #include <stdlib.h>
 
-// Persistent grid: one wave per SIMD.  Every walker takes the same few steps here, so a static split is balanced, and
-// each workgroup flushes a private deposit table (25 KB) at its end -- the fewer workgroups the less HBM traffic
-// (measured, 65536 walkers: 4096 workgroups 1.09 ms, 1024 workgroups 0.92 ms).
-static unsigned adj_grid(int64_t B, int G) { return ff_grid(B, G, 4 * ff_device_cus()); }
+// workgroups of a launch by its plan (ff_plan.h: a persistent grid of one workgroup per SIMD)
+static unsigned adj_grid(int64_t B, const ff_plan& p) { return ff_grid(B, p.wg_walkers(), p.cap(ff_device_cus(), false)); }
 
 // Direct-evaluation adjoint: a lane keeps the parameter integrands of MAXU of its hidden units in registers, so one launch
 // integrates the gradient of M*MAXU units (all of the reference's default width 50 at once); wider nets (--Deta/--Dmu up to
 // FF_HMAX, src/FermionHO2D.py:24-27) take one launch per chunk of units.
 template <int N, int D>
-static void launch_adj(void* stream, const ff_adj_args& a_in) {
+static void launch_adj(void* stream, const ff_adj_args& a_in, const ff_plan& p) {
   constexpr int M = ff_geom<N, D>::M;
   constexpr int MU_64 = (64 + M - 1) / M > 16 ? 16 : (64 + M - 1) / M, MU_50 = (50 + M - 1) / M > 16 ? 16 : (50 + M - 1) / M;
   const int hmax = a_in.net.He > a_in.net.Hm ? a_in.net.He : a_in.net.Hm;
@@ -812,13 +783,13 @@ static void launch_adj(void* stream, const ff_adj_args& a_in) {
   const size_t lds = sizeof(ff_adj_smem<N, D>);
   if (MU_50 < MU_64 && hmax <= MU_50 * M) {
     a.unit0 = 0;
-    if (lean) FF_LAUNCH_LDS((ff_ode_adj_lean_kernel<N, D, MU_50>), adj_grid(a.B, ff_geom<N, D>::G), FF_WAVE, lds, stream, a);
-    else FF_LAUNCH((ff_ode_adj_kernel<N, D, MU_50>), adj_grid(a.B, ff_geom<N, D>::G), FF_WAVE, stream, a);
+    if (lean) FF_LAUNCH_LDS((ff_ode_adj_lean_kernel<N, D, MU_50>), adj_grid(a.B, p), FF_WAVE, lds, stream, a);
+    else FF_LAUNCH((ff_ode_adj_kernel<N, D, MU_50>), adj_grid(a.B, p), FF_WAVE, stream, a);
   } else {
     for (int u0 = 0; u0 < hmax; u0 += MU_64 * M) {
       a.unit0 = u0;
-      if (lean) FF_LAUNCH_LDS((ff_ode_adj_lean_kernel<N, D, MU_64>), adj_grid(a.B, ff_geom<N, D>::G), FF_WAVE, lds, stream, a);
-      else FF_LAUNCH((ff_ode_adj_kernel<N, D, MU_64>), adj_grid(a.B, ff_geom<N, D>::G), FF_WAVE, stream, a);
+      if (lean) FF_LAUNCH_LDS((ff_ode_adj_lean_kernel<N, D, MU_64>), adj_grid(a.B, p), FF_WAVE, lds, stream, a);
+      else FF_LAUNCH((ff_ode_adj_kernel<N, D, MU_64>), adj_grid(a.B, p), FF_WAVE, stream, a);
     }
   }
 }
@@ -836,29 +807,32 @@ __global__ void __launch_bounds__(256) ff_open_steps_kernel(int64_t B, const dou
 
 extern "C" {
 
-static size_t adj_table_doubles(int64_t B, int Gtab) {   // one private table per workgroup of the tabulated kernel + Wtot
-  return (size_t)adj_grid(B, Gtab) * 2 * FF_DEP_NLDS * FF_DEP_ROW + (size_t)2 * FF_DEP_NTOT * FF_DEP_ROW;
+// The plans of a call (ff_plan.h): tab = the tabulated kernel, dir = the direct kernel behind it (for the wide family: its two kernels)
+struct adj_plans { ff_plan tab, dir; };
+static adj_plans adj_plan(int n, int d, bool wide_forced) {
+  ff_plan_knobs k;
+  k.wide_forced = wide_forced;
+  return {ff_plan_adjoint(n, d, false, k), ff_plan_adjoint(n, d, true, k)};
+}
+
+static size_t adj_table_doubles(int64_t B, const ff_plan& tab) {   // one private table per workgroup of the tabulated kernel + Wtot
+  return (size_t)adj_grid(B, tab) * 2 * FF_DEP_NLDS * FF_DEP_ROW + (size_t)2 * FF_DEP_NTOT * FF_DEP_ROW;
 }
 
 // workspace = [direct rows | private tables + Wtot | off-table flag]
-static size_t adj_direct_doubles(int64_t B, int G, int He, int Hm) { return (size_t)adj_grid(B, G) * G * (size_t)(3 * He + 3 * Hm); }
+static size_t adj_direct_doubles(int64_t B, const ff_plan& dir, int He, int Hm) { return (size_t)adj_grid(B, dir) * dir.group * (size_t)(3 * He + 3 * Hm); }
 
-// the narrow kernels are instantiated for the shapes of ff_ode.h (n = 1..12 in d = 2, n = 2..4 in d = 3); everything else (and
-// everything under FF_WIDE=1) goes to the one-walker-per-wave kernels of ff_adj_wide.h
-static bool adj_is_wide(int n, int d) { return ff_wide_supported(n, d) && (!ff_narrow_shape(n, d) || ff_wide_forced()); }
-
-// doubles of the layout one kernel family uses (0: that family does not serve (n, d))
-static size_t adj_ws_doubles(bool wide, int64_t B, int n, int d, int He, int Hm) {
-  if (wide) return ff_wide_supported(n, d) ? adj_direct_doubles(B, 1, He, Hm) + adj_table_doubles(B, 1) + 1 + (size_t)B : 0;   // (+ B: opening steps, ff_ode.walker_h_equal)
-  const int G = ff_geom_G(n, d);
-  return (ff_narrow_shape(n, d) && G) ? adj_direct_doubles(B, G, He, Hm) + adj_table_doubles(B, adj_tab_G(n, d) * FF_ADJ_WPW) + 1 : 0;
+// doubles of the layout one kernel family uses (0: no kernel serves the shape)
+static size_t adj_ws_doubles(const adj_plans& p, int64_t B, int He, int Hm) {
+  if (p.tab.family == FF_FAMILY_NONE) return 0;
+  return adj_direct_doubles(B, p.dir, He, Hm) + adj_table_doubles(B, p.tab) + 1 + (p.tab.family == FF_FAMILY_WIDE ? (size_t)B : 0);   // (+ B: opening steps, ff_ode.walker_h_equal)
 }
 
 // The larger of the two families' layouts: which family a call uses is decided when it runs (ff_set_kernel_family / FF_WIDE may
 // change between this query and the call, e.g. from another thread) -- a buffer of this size serves either.
 size_t ff_cnf_adjoint_workspace_bytes(int64_t B, int n, int d, int He, int Hm) {
   if (B <= 0) return 0;
-  const size_t a = adj_ws_doubles(false, B, n, d, He, Hm), b = adj_ws_doubles(true, B, n, d, He, Hm);
+  const size_t a = adj_ws_doubles(adj_plan(n, d, false), B, He, Hm), b = adj_ws_doubles(adj_plan(n, d, true), B, He, Hm);
   return sizeof(double) * (a > b ? a : b);
 }
 
@@ -894,15 +868,16 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
   ff_adj_args a = {};
   ff_fill_common(a, B, net, ode, true);
   a.z_in = z_t0; a.az_in = a_z; a.ad_in = a_d; a.w_e = w_e; a.w_mean = w_mean; a.w_index = w_index; a.w_scale = w_scale; a.gx_out = grad_x; a.rows = (double*)workspace; a.stats = stats;
-  const bool wide = adj_is_wide(n, d);      // the family of THIS call, read once: layout, memset and launches below all follow it
-  {
-    const int Gq = wide ? 1 : ff_geom_G(n, d);
-    if (Gq == 0) { ff_set_error("ff_cnf_adjoint: n*d > 64"); return FF_EUNSUPPORTED; }
-    a.trows = a.rows + adj_direct_doubles(B, Gq, net->He, net->Hm);
-    a.off_table = a.trows + adj_table_doubles(B, wide ? 1 : adj_tab_G(n, d) * FF_ADJ_WPW);
+  const adj_plans p = adj_plan(n, d, ff_wide_forced());      // the family of THIS call, read once: layout, memset and launches below all follow it
+  const bool wide = p.tab.family == FF_FAMILY_WIDE;
+  if (p.tab.family == FF_FAMILY_NONE) {      // (refused before anything is launched)
+    ff_set_error(ff_geom_G(n, d) == 0 ? "ff_cnf_adjoint: n*d > 64" : "fused CNF kernels serve n <= 24 particles with n*d <= 60 in d = 2, 3");
+    return FF_EUNSUPPORTED;
   }
+  a.trows = a.rows + adj_direct_doubles(B, p.dir, net->He, net->Hm);
+  a.off_table = a.trows + adj_table_doubles(B, p.tab);
   if (wide) {      // (those kernels accumulate in their global rows and tables)
-    if (hipMemsetAsync(workspace, 0, sizeof(double) * adj_ws_doubles(wide, B, n, d, net->He, net->Hm), (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
+    if (hipMemsetAsync(workspace, 0, sizeof(double) * adj_ws_doubles(p, B, net->He, net->Hm), (hipStream_t)stream) != hipSuccess) return FF_ELAUNCH;
   } else {
     // The narrow kernels write their private rows and tables in full; what must start at zero is the shared overflow table (Wtot:
     // global atomics for the nodes beyond the LDS tables) and the off-table flag behind it -- 98 KB by a kernel of our own: the
@@ -910,7 +885,6 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
     double* wt = a.off_table - (size_t)2 * FF_DEP_NTOT * FF_DEP_ROW;
     FF_LAUNCH(ff_zero_kernel, 48, 256, stream, wt, (size_t)2 * FF_DEP_NTOT * FF_DEP_ROW + 1);
   }
-  int G = 0;
   if (wide && a.h_equal && a.h_init) {
     const int64_t nh = a.h_scale < 0.0 ? 1 : B;      // (walker_h_uniform: one entry)
     double* hs = a.off_table + 1;
@@ -920,21 +894,17 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
   if (wide) {
     // lanes per walker: two waves up to 128 radii (pairs + one-body), four beyond; one radius per lane up to 22 particles
     const int nr = n * (n + 1) / 2, Wv = nr <= 128 ? 2 : 4, nq = (nr + 64 * Wv - 1) / (64 * Wv);
-    const unsigned grid = adj_grid(a.B, 1);
+    const unsigned grid = adj_grid(a.B, p.tab);
 #define FF_WA(D_, W_, Q_) if (d == D_ && Wv == W_ && nq == Q_) { if (net->radial_table) FF_LAUNCH((ff_wide_adjtab_kernel<D_, W_, Q_>), grid, FF_WAVE * W_, stream, a, n); \
-                                                                  FF_LAUNCH((ff_wide_adj_kernel<D_, W_, Q_>), grid, FF_WAVE * W_, stream, a, n); G = 1; }
+                                                                  FF_LAUNCH((ff_wide_adj_kernel<D_, W_, Q_>), grid, FF_WAVE * W_, stream, a, n); }
     FF_WA(2, 2, 1) FF_WA(2, 4, 1) FF_WA(2, 4, 2) FF_WA(3, 2, 1) FF_WA(3, 4, 1) FF_WA(3, 4, 2)
 #undef FF_WA
   } else {
     // both variants are enqueued; on the device exactly one of them runs, chosen by the radial-table header
     // (no table / weights too stiff for the deposit grid -> direct evaluation), so the host never has to look at it
-#define FF_ND(N_, D_) if (n == N_ && d == D_) { if (net->radial_table) FF_LAUNCH((ff_ode_adjtab_kernel<N_, D_, FF_ADJ_WPW>), adj_grid(a.B, ff_adjtab_geom<N_, D_>::G * FF_ADJ_WPW), FF_WAVE * FF_ADJ_WPW, stream, a); launch_adj<N_, D_>(stream, a); G = ff_geom<N_, D_>::G; }
-    FF_NARROW_COLUMNS(FF_ND) FF_NARROW_ROWS_ONLY(FF_ND)
+#define FF_ND(N_, D_, S_) if (n == N_ && d == D_) { if (net->radial_table) FF_LAUNCH((ff_ode_adjtab_kernel<N_, D_, FF_ADJ_WPW>), adj_grid(a.B, p.tab), FF_WAVE * FF_ADJ_WPW, stream, a); launch_adj<N_, D_>(stream, a, p.dir); }
+    FF_NARROW_SHAPES(FF_ND)
 #undef FF_ND
-  }
-  if (G == 0) {
-    ff_set_error("fused CNF kernels serve n <= 24 particles with n*d <= 60 in d = 2, 3");
-    return FF_EUNSUPPORTED;
   }
   FF_LAUNCH_CHECK();
   // ff_ode.after_main_event: whoever waits for it runs under the small kernels below, not beside the one above
@@ -942,9 +912,9 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
     ff_set_error("ff_cnf_adjoint: hipEventRecord(after_main_event) failed");
     return FF_ELAUNCH;
   }
-  const int nblk = (int)adj_grid(B, G);
+  const int nblk = (int)adj_grid(B, p.dir), G = p.dir.group;
   {
-    const int ntab = (int)adj_grid(B, wide ? 1 : adj_tab_G(n, d) * FF_ADJ_WPW);     // workgroups (= private tables) of the tabulated kernel
+    const int ntab = (int)adj_grid(B, p.tab);     // workgroups (= private tables) of the tabulated kernel
     double* wtot = a.trows + (size_t)ntab * 2 * FF_DEP_NLDS * FF_DEP_ROW;
     const unsigned ndep = net->radial_table ? (unsigned)((2 * FF_DEP_NLDS * FF_DEP_ROW + FF_DEPR_EX - 1) / FF_DEPR_EX) : 0u;
     FF_LAUNCH(ff_adj_reduce_kernel, (unsigned)P + ndep, FF_DEPR_EX * FF_DEPR_TY, stream, *net, (const double*)a.off_table, nblk * G, P,
@@ -952,7 +922,7 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
     FF_LAUNCH_CHECK();
   }
   if (net->radial_table) {
-    const int ntab = (int)adj_grid(B, wide ? 1 : adj_tab_G(n, d) * FF_ADJ_WPW);
+    const int ntab = (int)adj_grid(B, p.tab);
     double* wtot = a.trows + (size_t)ntab * 2 * FF_DEP_NLDS * FF_DEP_ROW;
     FF_LAUNCH(ff_dep_contract_kernel, (unsigned)(net->He + net->Hm), FF_RBLOCK(256), stream, *net, (const double*)a.off_table,
               (const double*)wtot, grad_params);

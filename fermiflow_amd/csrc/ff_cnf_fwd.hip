@@ -100,8 +100,10 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
   __shared__ __attribute__((aligned(16))) double s_qt[JET ? G * M * QTW : 1];
   __shared__ int s_pa[R], s_pb[R], s_any;
   __shared__ double s_rmin[G][R];   // smallest value each radius took during the walker's integration (walker_cost)
-  // lane-private LDS columns for y and the error accumulator: only while 4 workgroups still fit a CU's LDS
-  constexpr bool LDS_STATE = (MODE == 2 && M <= 12);
+  // lane-private LDS columns for y and the error accumulator; 4 workgroups still fit a CU's LDS up to 12 coordinates, and the
+  // local-energy pass of nothing larger comes here (ff_plan.h: FF_ELOC_COLUMNS)
+  static_assert(MODE != 2 || M <= 12, "the column-sweep local-energy kernel serves at most 12 coordinates");
+  constexpr bool LDS_STATE = (MODE == 2);
   __shared__ double s_yv[LDS_STATE ? NV : 1][FF_WAVE], s_cv[LDS_STATE ? NV : 1][FF_WAVE];
 
   const int lane = threadIdx.x;
@@ -388,8 +390,7 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
         const double* u = &in[1];
         // the records stream through a two-deep register buffer: the LDS reads of chunk c+1 are issued before chunk c
         // is computed, so the single resident wave does not sit out an LDS round trip per radius
-        constexpr bool PREF = (M <= 12);   // look-ahead only where the registers are there for it
-        constexpr int CH = PREF ? FF_SWEEP_CH : 2, RT = P + N, NCH = (RT + CH - 1) / CH;
+        constexpr int CH = FF_SWEEP_CH, RT = P + N, NCH = (RT + CH - 1) / CH;
         constexpr ff_pair_table<N> PT{};
         double hb[2][CH][RECW];
         auto load_chunk = [&](int c, double (*buf)[RECW]) {
@@ -402,18 +403,17 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
             }
           }
         };
-        if constexpr (PREF) load_chunk(0, hb[0]);
+        load_chunk(0, hb[0]);
 #pragma unroll
         for (int c = 0; c < NCH; c++) {
-          if constexpr (PREF) { if (c + 1 < NCH) load_chunk(c + 1, hb[(c + 1) & 1]); }
-          else load_chunk(c, hb[0]);
+          if (c + 1 < NCH) load_chunk(c + 1, hb[(c + 1) & 1]);
 #pragma unroll
           for (int q = 0; q < CH; q++) {
             const int p = c * CH + q;
             if (p < RT && (p < P || has_mu)) {
               const bool pair = p < P;
               const int a = pair ? PT.a[p < P ? p : 0] : p - P, bq = pair ? PT.b[p < P ? p : 0] : 0;
-              const double* hq = hb[PREF ? (c & 1) : 0][q];
+              const double* hq = hb[c & 1][q];
               const double* rho = hq;
               const double ri = hq[D], f0 = hq[D + 1], f1 = hq[D + 2], f2 = hq[D + 3], Ac = hq[D + 4], Bc = hq[D + 5];
               double dl[D], rd = 0.0, dd = 0.0;
@@ -1337,14 +1337,12 @@ extern int ff_slater_rows_launch(void* stream, int d, int64_t B, int nup, int nd
 #include <string.h>
 #include <mutex>
 #include <vector>
-static constexpr int64_t FF_GRID_CAP = 1 << 20;      // without a work queue: one workgroup per walker group, up to this many
 
 // With a radial table: the table kernel, then the direct-evaluation kernel as its (normally idle) fallback -- it returns
 // in its first instructions unless the table kernel left this launch's id in the event slot.  Without: direct only.
-// Grid of a launch that takes G walkers per workgroup: with a work queue a persistent grid of `wps` waves per SIMD (four SIMDs per
-// CU), without one a workgroup per walker group
-static unsigned fwd_grid(const ff_fwd_args& a, int G, int wps = 1) {
-  return ff_grid(a.B, G, a.queue ? wps * 4 * ff_device_cus() : FF_GRID_CAP);
+// Grid of a launch by its plan (ff_plan.h): with a work queue a persistent grid, without one a workgroup per walker group
+static unsigned fwd_grid(const ff_fwd_args& a, const ff_plan& p) {
+  return ff_grid(a.B, p.group, p.cap(ff_device_cus(), a.queue != nullptr));
 }
 
 // Routing of the local-energy pass by cost class.  A launch cannot end before its longest chain of steps has: a walker with a
@@ -1400,10 +1398,9 @@ static int eloc_finish_impl(void* stream, int64_t B, int nup, int ndn, const int
                             double* glogp0_out, ff_fin_filter flt);
 }
 enum { FF_ROUTE_NONE = 0, FF_ROUTE_DONE = 1, FF_ROUTE_FAILED = 2 };
-// What the local-energy dispatch of THIS host thread did, for ff_eloc to read back right after it: did the kernel it chose take the
+// What the local-energy dispatch did, for ff_eloc_nd (which passes it in) to read right after it: did the kernel it chose take the
 // fused finish (ff_fwd_args::fin), and was the pass routed (then the walkers of class >= heavy_class still need the finish kernels).
 struct ff_eloc_feedback { bool fused, routed; const double* evt; double evt_id; };
-static thread_local ff_eloc_feedback t_eloc_fb = {false, false, nullptr, 0.0};
 // launch_table(stream, args): the table kernel of the throughput family.
 // FF_ROUTE_DONE: both launches are enqueued and joined (the caller's fallback launch then redoes EVERY walker should it have to run:
 // heavy_mode stays 0 in its arguments).  FF_ROUTE_NONE: nothing was launched -- no classes, routing switched off, no side stream, or
@@ -1414,7 +1411,7 @@ static thread_local ff_eloc_feedback t_eloc_fb = {false, false, nullptr, 0.0};
 // fin.on): otherwise the caller's unfiltered finish kernels run over every walker and need the heavy walkers' sensitivities in the workspace.
 template <class F>
 static int launch_routed(void* stream, int n, int d, const ff_fwd_args& a, F launch_table, bool throughput_fuses) {
-  if (!(a.evt && a.wclass && a.heavy_class > 0 && n * d <= 12 && ff_wide_supported(n, d))) return FF_ROUTE_NONE;
+  if (!(a.evt && a.wclass && a.heavy_class > 0 && n * d <= 12 && ff_wide_shape(n, d))) return FF_ROUTE_NONE;
   std::lock_guard<std::mutex> lock(g_side_mutex);
   ff_side_lane* side = ff_side();
   if (!side || hipEventRecord(side->fork, (hipStream_t)stream) != hipSuccess || hipStreamWaitEvent(side->stream, side->fork, 0) != hipSuccess) {
@@ -1464,62 +1461,66 @@ static int launch_routed(void* stream, int n, int d, const ff_fwd_args& a, F lau
 }
 
 template <int N, int D, int MODE>
-static int launch_fwd(void* stream, const ff_fwd_args& a) {
-  const unsigned grid = fwd_grid(a, ff_geom<N, D>::G);
+static int launch_fwd(void* stream, const ff_fwd_args& a, const ff_plan& p, const ff_plan& fb) {
+  const unsigned grid = fwd_grid(a, p);
   auto table = [&](void* st, const ff_fwd_args& aa) { FF_LAUNCH((ff_ode_fwd_kernel<N, D, MODE, true>), grid, FF_WAVE, st, aa); };
   int routed = FF_ROUTE_NONE;
   if constexpr (MODE == 2 && N <= 3) routed = launch_routed(stream, N, D, a, table, false);
   if (routed == FF_ROUTE_FAILED) return FF_ELAUNCH;
   if (routed == FF_ROUTE_NONE && a.evt) table(stream, a);
-  // behind a table kernel the direct kernel is a fallback that almost always finds nothing to do: a grid-stride launch of two waves per
-  // SIMD instead of one workgroup per walker group (13 108 workgroups at config 2: 6 us just to start and retire them)
-  const unsigned grid_fb = a.evt && grid > 2048u ? 2048u : grid;
+  // (without a table the direct kernel is the call: the table kernel's grid)
+  const unsigned grid_fb = a.evt && grid > fwd_grid(a, fb) ? fwd_grid(a, fb) : grid;
   FF_LAUNCH((ff_ode_fwd_kernel<N, D, MODE, false>), grid_fb, FF_WAVE, stream, a);
   return FF_OK;
 }
 
-// n >= 8 uses the two-lanes-per-direction local-energy kernel (measured, 32768 walkers: n = 8 6.5 -> 4.5 ms,
-// n = 10 48 -> 9.3 ms, n = 12 95 -> 14.7 ms)
 template <int N, int D>
-static void launch_split(void* stream, const ff_fwd_args& a) {
-  const unsigned grid = fwd_grid(a, FF_WAVE / (2 * N * D));
+static void launch_split(void* stream, const ff_fwd_args& a, const ff_plan& p) {
+  const unsigned grid = fwd_grid(a, p);
   if (a.evt) FF_LAUNCH((ff_eloc_split_kernel<N, D, true>), grid, FF_WAVE, stream, a);
   FF_LAUNCH((ff_eloc_split_kernel<N, D, false>), grid, FF_WAVE, stream, a);
 }
 
-// Row-layout local-energy kernel (ff_eloc_rows.h): SPLIT lanes per row chosen so that a walker group fills the wave and
-// the workgroup's LDS stays under 40 KB (four single-wave workgroups per CU)
+// Row-layout local-energy kernel (ff_eloc_rows.h), SPLIT lanes per row
 template <int N, int D, int SPLIT>
-static void launch_rows(void* stream, const ff_fwd_args& a) {
-  constexpr int G = FF_WAVE / (N * D * SPLIT) > 16 ? 16 : FF_WAVE / (N * D * SPLIT);
-  const unsigned grid = fwd_grid(a, G);
+static void launch_rows(void* stream, const ff_fwd_args& a, const ff_plan& p) {
+  const unsigned grid = fwd_grid(a, p);
   if (a.evt) FF_LAUNCH((ff_eloc_rows_kernel<N, D, SPLIT, true>), grid, FF_WAVE, stream, a);
   FF_LAUNCH((ff_eloc_rows_kernel<N, D, SPLIT, false>), grid, FF_WAVE, stream, a);
 }
 
-#ifndef FF_MFMA_WPS
-#define FF_MFMA_WPS 2   // waves per SIMD the matrix-core kernel is compiled for (A/B knob)
-#endif
-// Matrix-core local-energy kernel (ff_eloc_mfma.h): four walkers per wave, M = n d <= 12, two waves per SIMD
+// Matrix-core local-energy kernel (ff_eloc_mfma.h): four walkers per wave, M = n d <= 12, FF_MFMA_WPS waves per SIMD
 template <int N, int D>
-static int launch_mfma(void* stream, const ff_fwd_args& a) {
+static int launch_mfma(void* stream, const ff_fwd_args& a, const ff_plan& p, const ff_plan& fb, ff_eloc_feedback& out) {
   auto table = [&](void* st, const ff_fwd_args& aa) {
-    FF_LAUNCH((ff_eloc_mfma_kernel<N, D, true, FF_MFMA_WPS>), fwd_grid(a, 4, FF_MFMA_WPS), FF_WAVE, st, aa);
+    FF_LAUNCH((ff_eloc_mfma_kernel<N, D, true, FF_MFMA_WPS>), fwd_grid(a, p), FF_WAVE, st, aa);
   };
   const int routed = launch_routed(stream, N, D, a, table, (a.fin.on & 1) && N % 2 == 0 && D == 2);
   if (routed == FF_ROUTE_FAILED) return FF_ELAUNCH;
   if (routed == FF_ROUTE_NONE && a.evt) table(stream, a);
-  t_eloc_fb.fused = (a.fin.on & 1) && N % 2 == 0 && D == 2;      // (what the kernel's epilogue tests)
-  t_eloc_fb.routed = routed == FF_ROUTE_DONE;
-  t_eloc_fb.evt = a.evt; t_eloc_fb.evt_id = a.evt_id;
-  FF_LAUNCH((ff_eloc_mfma_kernel<N, D, false, 1>), fwd_grid(a, 4), FF_WAVE, stream, a);
+  out = {(a.fin.on & 1) && N % 2 == 0 && D == 2, routed == FF_ROUTE_DONE, a.evt, a.evt_id};      // (fused: what the kernel's epilogue tests)
+  FF_LAUNCH((ff_eloc_mfma_kernel<N, D, false, 1>), fwd_grid(a, fb), FF_WAVE, stream, a);
   return FF_OK;
 }
 
 static std::atomic<uint64_t> g_evt_counter{1};
 
+// the knobs of this process: FF_ELOC_KERNEL (read once) and the kernel family as it stands now
+static ff_plan_knobs fwd_knobs() {
+  static const int eloc_kind = [] {
+    const char* e = getenv("FF_ELOC_KERNEL");
+    return !e ? FF_ELOC_AUTO : (!strcmp(e, "mfma") ? FF_ELOC_MFMA : (!strcmp(e, "rows") ? FF_ELOC_ROWS : (!strcmp(e, "columns") ? FF_ELOC_COLUMNS : (!strcmp(e, "wide") ? FF_ELOC_WIDE : FF_ELOC_AUTO))));
+  }();
+  ff_plan_knobs k;
+  k.eloc_kind = eloc_kind;
+  k.wide_forced = ff_wide_forced();
+  return k;
+}
+
+// MODE 0 CNF.generate, 1 CNF.delta_logp, 2 local-energy sensitivities (`fb`: what the pass did, for ff_eloc_nd).  The plan of
+// ff_plan.h names the family; the lists there name the shapes it is instantiated for.
 template <int MODE>
-static int dispatch_fwd(void* stream, int n, int d, const ff_fwd_args& a_in) {
+static int dispatch_fwd(void* stream, int n, int d, const ff_fwd_args& a_in, ff_eloc_feedback* fb_out = nullptr) {
   ff_fwd_args a = a_in;
   a.evt = nullptr;
   a.evt_id = 0.0;
@@ -1528,52 +1529,51 @@ static int dispatch_fwd(void* stream, int n, int d, const ff_fwd_args& a_in) {
     a.evt = const_cast<double*>(a.net.radial_table) + FF_TAB_EVT0 + (id % FF_TAB_NEVT);
     a.evt_id = (double)(id & ((1ull << 52) - 1)) + 1.0;
   }
-  // Local-energy pass: three kernels compute it (tests/test_hostsim.py::test_three_local_energy_kernels_agree);
-  // FF_ELOC_KERNEL = auto (default) | mfma | rows | columns forces one where it is instantiated.  auto takes the fastest
-  // measured on MI355X (tools/probes/eloc_ab.py): the column sweep up to 8 particles, the row layout from 9 on (and for
-  // every particle number the column sweep is not instantiated for).
-  auto wide = [&]() -> int {      // the one-walker-per-workgroup family; its local-energy kernels take the fused finish (bit 1 of fin.on)
-    const int st_ = ff_wide_dispatch_fwd(MODE, stream, n, d, a);
-    if (MODE == 2 && st_ == FF_OK) { t_eloc_fb.fused = (a.fin.on & 2) != 0; t_eloc_fb.routed = false; }
-    return st_;
-  };
-  if (ff_wide_forced() && ff_wide_supported(n, d)) return wide();   // FF_WIDE=1: A/B and parity testing
-  static const int eloc_kind = [] {
-    const char* e = getenv("FF_ELOC_KERNEL");
-    return !e ? 0 : (!strcmp(e, "mfma") ? 1 : (!strcmp(e, "rows") ? 2 : (!strcmp(e, "columns") ? 3 : (!strcmp(e, "wide") ? 4 : 0))));
-  }();
-  // one walker per workgroup, both products on v_mfma_f64_16x16x4 (ff_wide.hip): measured faster than the row layout from
-  // 11 particles on (tools/probes/wide_c5.py; 16 384 walkers: 11 particles 2.12 against 2.68 ms, 12 particles 2.25 against 2.91; 10 particles 2.04 against 1.88)
-  constexpr int wide_from = 11;
-  if (MODE == 2 && d == 2 && (eloc_kind == 4 || (eloc_kind == 0 && n >= wide_from)) && ff_wide_supported(n, d))
-    return wide();
-#ifndef FF_MFMA_FROM
-#define FF_MFMA_FROM 4      // (2-3 particles tie with the column sweep and keep it: DESIGN.md 3g; the host simulator builds with 99)
-#endif
-  constexpr int mfma_from = FF_MFMA_FROM;
-  if (MODE == 2 && (eloc_kind == 1 || (eloc_kind == 0 && d == 2 && n >= mfma_from && n <= 6))) {
-#define FF_MF(N_, D_) if (n == N_ && d == D_) { const int s_ = launch_mfma<N_, D_>(stream, a); if (s_) return s_; FF_LAUNCH_CHECK(); return FF_OK; }
-    FF_MF(6, 2) FF_MF(2, 2) FF_MF(3, 2) FF_MF(4, 2) FF_MF(5, 2)
+  const ff_plan_knobs k = fwd_knobs();
+  const ff_plan p = MODE == 2 ? ff_plan_eloc(n, d, false, k) : ff_plan_flow(n, d, false, k);
+  const ff_plan fb = MODE == 2 ? ff_plan_eloc(n, d, true, k) : ff_plan_flow(n, d, true, k);
+  ff_eloc_feedback unused, &out = fb_out ? *fb_out : unused;
+  out = {false, false, nullptr, 0.0};
+  int st = FF_OK;
+  switch (p.family) {
+    case FF_FAMILY_WIDE:      // its local-energy kernels take the fused finish on request (bit 1 of fin.on)
+      st = ff_wide_dispatch_fwd(MODE, stream, n, d, a, p);
+      if (MODE == 2 && st == FF_OK) out.fused = (a.fin.on & 2) != 0;
+      return st;
+    case FF_FAMILY_MFMA:
+#define FF_MF(N_, D_) if (n == N_ && d == D_) st = launch_mfma<N_, D_>(stream, a, p, fb, out);
+      FF_ELOC_MFMA(FF_MF)
 #undef FF_MF
-  }
-  if (MODE == 2 && (eloc_kind == 2 || ff_narrow_rows_only(n, d) || (eloc_kind == 0 && n >= 9))) {
-#define FF_RW(N_, D_, S_) if (n == N_ && d == D_) { launch_rows<N_, D_, S_>(stream, a); FF_LAUNCH_CHECK(); return FF_OK; }
-    FF_RW(6, 2, 1) FF_RW(2, 2, 1) FF_RW(3, 2, 1) FF_RW(4, 2, 1) FF_RW(5, 2, 1) FF_RW(7, 2, 2) FF_RW(8, 2, 2) FF_RW(9, 2, 3)
-    FF_RW(10, 2, 3) FF_RW(11, 2, 2) FF_RW(12, 2, 2) FF_RW(1, 2, 1)
-    FF_RW(2, 3, 1) FF_RW(3, 3, 1) FF_RW(4, 3, 1)      // three dimensions (small systems; finish: ff_eloc_finish3d)
+      break;
+    case FF_FAMILY_ROWS:
+#define FF_RW(N_, D_, S_) if (n == N_ && d == D_) launch_rows<N_, D_, S_>(stream, a, p);
+      FF_NARROW_SHAPES(FF_RW)
 #undef FF_RW
-  }
-  if (MODE == 2 && d == 2) {
-#define FF_SP(N_) if (n == N_) { launch_split<N_, 2>(stream, a); FF_LAUNCH_CHECK(); return FF_OK; }
-    FF_SP(8) FF_SP(10) FF_SP(12)
+      break;
+    case FF_FAMILY_SPLIT:
+#define FF_SP(N_, D_) if (n == N_ && d == D_) launch_split<N_, D_>(stream, a, p);
+      FF_ELOC_SPLIT(FF_SP)
 #undef FF_SP
-  }
-#define FF_ND(N_, D_) if (n == N_ && d == D_) { const int s_ = launch_fwd<N_, D_, MODE>(stream, a); if (s_) return s_; FF_LAUNCH_CHECK(); return FF_OK; }
-  FF_NARROW_COLUMNS(FF_ND)
-  if constexpr (MODE != 2) { FF_NARROW_ROWS_ONLY(FF_ND) }   // (their local-energy pass is the row-layout kernel above)
+      break;
+    case FF_FAMILY_COLUMNS:
+#define FF_ND(N_, D_) if (n == N_ && d == D_) st = launch_fwd<N_, D_, 2>(stream, a, p, fb);
+      FF_ELOC_COLUMNS(FF_ND)
 #undef FF_ND
-  // everything else: one walker per workgroup (ff_wide.hip: n <= 24, n d <= 60)
-  return wide();
+      break;
+    case FF_FAMILY_NARROW:
+      if constexpr (MODE != 2) {
+#define FF_ND(N_, D_, S_) if (n == N_ && d == D_) st = launch_fwd<N_, D_, MODE>(stream, a, p, fb);
+        FF_NARROW_SHAPES(FF_ND)
+#undef FF_ND
+      }
+      break;
+    default:
+      ff_set_error("fused CNF kernels serve n <= 24 particles with n*d <= 60 in d = 2, 3");
+      return FF_EUNSUPPORTED;
+  }
+  if (st) return st;
+  FF_LAUNCH_CHECK();
+  return FF_OK;
 }
 
 extern "C" {
@@ -1633,7 +1633,7 @@ size_t ff_eloc_nd_workspace_bytes(int64_t B, int n, int d, int compact_finish) {
 }
 
 static int eloc_sensitivities_impl(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* x,
-                                   void* workspace, int32_t* stats, const ff_fwd_args::ff_fin_args* fin);
+                                   void* workspace, int32_t* stats, const ff_fwd_args::ff_fin_args* fin, ff_eloc_feedback* fb);
 }
 // the two work counters of a launch (table kernel, direct fallback) back to zero
 __global__ void ff_queue_reset_kernel(unsigned long long* q) { if (threadIdx.x < 2) q[threadIdx.x] = 0ULL; }
@@ -1642,12 +1642,11 @@ extern "C" {
 /* pass 1 of ff_eloc: the fused sensitivity integration (results stay in `workspace`) */
 int ff_eloc_sensitivities(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* x,
                           void* workspace, int32_t* stats) {
-  return eloc_sensitivities_impl(stream, B, n, d, net, ode, x, workspace, stats, nullptr);
+  return eloc_sensitivities_impl(stream, B, n, d, net, ode, x, workspace, stats, nullptr, nullptr);
 }
 
 static int eloc_sensitivities_impl(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* x,
-                                   void* workspace, int32_t* stats, const ff_fwd_args::ff_fin_args* fin) {
-  t_eloc_fb = {false, false, nullptr, 0.0};
+                                   void* workspace, int32_t* stats, const ff_fwd_args::ff_fin_args* fin, ff_eloc_feedback* fb) {
   if (const int st = ff_check_flow("ff_cnf", B >= 0 && n > 0 && d > 0, net, ode)) return st;
   FF_CHECK(x && workspace, FF_EINVAL, "ff_eloc_sensitivities: null pointer");
   if (B == 0) return FF_OK;
@@ -1664,7 +1663,7 @@ static int eloc_sensitivities_impl(void* stream, int64_t B, int n, int d, const 
   if (fin) a.fin = *fin;
   FF_LAUNCH(ff_queue_reset_kernel, 1, FF_WAVE, stream, w.queue);      // (a kernel of our own, not hipMemsetAsync: 1 us instead of a 5 us blit + 8 us of bubble)
   a.queue = w.queue;
-  return dispatch_fwd<2>(stream, n, d, a);
+  return dispatch_fwd<2>(stream, n, d, a, fb);
 }
 
 /* pass 2 of ff_eloc: Slater gradient/Hessian contraction, potentials, E_loc */
@@ -1731,9 +1730,9 @@ int ff_eloc_nd(void* stream, int64_t B, int nup, int ndn, int d, const int32_t* 
   fin.on = ((d == 2 && nup == ndn && nup >= 1 && nup <= 3) ? 1 : 0) | ((ode && ode->compact_finish) ? 2 : 0);
   fin.nup = nup; fin.ndn = ndn; fin.use_ho = use_ho; fin.tab_up = tab_up; fin.tab_dn = tab_dn; fin.wstate = walker_state; fin.Z = Z;
   fin.logp = logp; fin.grad = grad; fin.lap = lap; fin.V = V; fin.eloc = eloc; fin.glogp0 = glogp0_out; fin.workspace = workspace;
-  int st = eloc_sensitivities_impl(stream, B, n, d, net, ode, x, workspace, stats, &fin);
+  ff_eloc_feedback fb = {false, false, nullptr, 0.0};
+  int st = eloc_sensitivities_impl(stream, B, n, d, net, ode, x, workspace, stats, &fin, &fb);
   if (st) return st;
-  const ff_eloc_feedback fb = t_eloc_fb;
   if (B == 0) return FF_OK;
   if (!fb.fused) {
     FF_CHECK(!compact, FF_EUNSUPPORTED, "ff_eloc: compact_finish, but the kernel of this shape has no fused finish");

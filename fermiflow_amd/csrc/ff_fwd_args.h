@@ -2,6 +2,7 @@
 // ff_wide.hip: one walker per workgroup) and the hand-over between the two translation units.
 #pragma once
 #include "ff_common.h"
+#include "ff_plan.h"
 
 struct ff_fwd_args {
   int64_t B;
@@ -57,9 +58,8 @@ struct ff_fwd_args {
 
 // Kernels for walkers that do not fit one wave's column / row layouts (n > 12 in d = 2, n > 4 in d = 3): ff_wide.hip.
 // mode: 0 CNF.generate, 1 CNF.delta_logp, 2 local-energy sensitivities.  Returns FF_OK / FF_EUNSUPPORTED / FF_ELAUNCH.
-int ff_wide_dispatch_fwd(int mode, void* stream, int n, int d, const ff_fwd_args& a);
-// nonzero if the wide family serves (n, d)
-int ff_wide_supported(int n, int d);
+// p: the plan that chose the family (ff_plan_flow / ff_plan_eloc, FF_FAMILY_WIDE): its grid cap and, for mode 2, T = p.param
+int ff_wide_dispatch_fwd(int mode, void* stream, int n, int d, const ff_fwd_args& a, const ff_plan& p);
 // the local-energy kernel of the family for the walkers a launch with heavy_mode = 1 selects: at most `max_groups` single-walker workgroups
 int ff_wide_eloc_heavy(void* stream, int n, int d, const ff_fwd_args& a, int64_t max_groups);
 // FF_WIDE=1 in the environment routes EVERY particle number to the wide family (A/B and parity testing)

@@ -12,22 +12,7 @@
 // whole flattened batch -- SURVEY.md finding 3: E_loc is insensitive to the step sequence (1e-10 relative).
 #pragma once
 #include "ff_common.h"
-
-// walkers per wave (at most 16: the radius ids carry 4 bits of it); 0: a walker does not fit one wave
-constexpr int ff_geom_G(int n, int d) {
-  const int M = n * d;
-  return M > 0 && M <= FF_WAVE ? (FF_WAVE / M > 16 ? 16 : FF_WAVE / M) : 0;
-}
-
-// The (N, D) the several-walkers-per-wave ("narrow") kernel families are instantiated for: X(N, D) over the shapes that have a
-// column-sweep local-energy kernel (ff_ode_fwd_kernel MODE 2), then over those whose local-energy pass is the row-layout kernel only.
-// The forward dispatch and the adjoint's both run through them in this order.
-#define FF_NARROW_COLUMNS(X) X(6, 2) X(3, 2) X(12, 2) X(2, 2) X(4, 2) X(5, 2) X(8, 2) X(10, 2)
-#define FF_NARROW_ROWS_ONLY(X) X(1, 2) X(7, 2) X(9, 2) X(11, 2) X(2, 3) X(3, 3) X(4, 3)
-#define FF_SHAPE_IS(N_, D_) || (n == N_ && d == D_)
-constexpr bool ff_narrow_rows_only(int n, int d) { return false FF_NARROW_ROWS_ONLY(FF_SHAPE_IS); }
-constexpr bool ff_narrow_shape(int n, int d) { return ff_narrow_rows_only(n, d) FF_NARROW_COLUMNS(FF_SHAPE_IS); }
-#undef FF_SHAPE_IS
+#include "ff_plan.h"      // ff_geom_G and the shapes each kernel family is instantiated for
 
 template <int N, int D>
 struct ff_geom {

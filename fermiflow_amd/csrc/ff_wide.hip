@@ -43,8 +43,6 @@
 #define FF_STAMP(i) do { } while (0)
 #endif
 
-#define FF_WIDE_NMAX 24
-#define FF_WIDE_MMAX 60
 #define FF_WIDE_RMAX (FF_WIDE_NMAX * (FF_WIDE_NMAX + 1) / 2)   // pairs + one-body radii
 
 // radius q of a walker with n particles (pairs a < b in a-major order, then the one-body radii) -> a | b << 5 | q << 10
@@ -1001,13 +999,12 @@ extern "C" int ff_set_kernel_family(int family) {
   return prev;
 }
 
-int ff_wide_supported(int n, int d) {
-  return (d == 2 || d == 3) && n >= 1 && n <= FF_WIDE_NMAX && n * d <= FF_WIDE_MMAX;
-}
+// the grid of a launch by its plan (ff_plan.h: persistent when the launch has a work queue -- as many workgroups as stay resident)
+static unsigned wide_grid(const ff_fwd_args& a, const ff_plan& p) { return ff_grid(a.B, p.group, p.cap(ff_device_cus(), a.queue != nullptr)); }
 
 template <int D, int MODE>
-static void launch_wide_flow(void* stream, const ff_fwd_args& a, int n) {
-  const unsigned grid = ff_grid(a.B, 1, 64 * ff_device_cus());
+static void launch_wide_flow(void* stream, const ff_fwd_args& a, int n, const ff_plan& p) {
+  const unsigned grid = wide_grid(a, p);
   if (a.evt) FF_LAUNCH((ff_wide_flow_kernel<D, MODE, true>), grid, FF_WAVE, stream, a, n);
   FF_LAUNCH((ff_wide_flow_kernel<D, MODE, false>), grid, FF_WAVE, stream, a, n);
 }
@@ -1023,10 +1020,8 @@ static void wide_with_fin(const ff_fwd_args& a, F launch) {
 }
 
 template <int D, int T, bool FIN>
-static void launch_wide_eloc(void* stream, const ff_fwd_args& a, int n) {
-  // persistent grid when the launch has a work queue: as many workgroups as stay resident (one per CU at T = 4)
-  const int64_t per_cu = T >= 3 ? 1 : (T == 2 ? 2 : 4);
-  const unsigned grid = ff_grid(a.B, 1, a.queue ? per_cu * ff_device_cus() : ((int64_t)1 << 20));
+static void launch_wide_eloc(void* stream, const ff_fwd_args& a, int n, const ff_plan& p) {
+  const unsigned grid = wide_grid(a, p);
   // single-precision sensitivities (ff_set_sens_precision(32)): the table kernel with J, A, S in fp32; its fallback stays fp64
   if (a.evt && ff_wide_sens_fp32() && T >= 2) FF_LAUNCH((ff_wide_eloc_kernel<D, (T >= 2 ? T : 2), true, float, FIN>), grid, FF_WAVE * T, stream, a, n);
   else if (a.evt) FF_LAUNCH((ff_wide_eloc_kernel<D, T, true, double, FIN>), grid, FF_WAVE * T, stream, a, n);
@@ -1034,7 +1029,7 @@ static void launch_wide_eloc(void* stream, const ff_fwd_args& a, int n) {
 }
 
 int ff_wide_eloc_heavy(void* stream, int n, int d, const ff_fwd_args& a, int64_t max_groups) {
-  if (!ff_wide_supported(n, d) || (n * d + 4 + 15) / 16 != 1 || !a.evt || a.queue) return FF_EUNSUPPORTED;   // (table kernel, T = 1, grid-stride)
+  if (!ff_wide_shape(n, d) || ff_wide_T(n, d) != 1 || !a.evt || a.queue) return FF_EUNSUPPORTED;   // (table kernel, T = 1, grid-stride)
 #ifdef FF_WIDE_NO_FIN      // (diagnostic build without the fused-finish instantiations: a caller that counts on them must hear it -- ADVICE r04)
   if (a.fin.on & 2) { ff_set_error("this build (FF_WIDE_NO_FIN) has no fused finish: ff_ode.compact_finish is not available"); return FF_EUNSUPPORTED; }
 #endif
@@ -1047,19 +1042,15 @@ int ff_wide_eloc_heavy(void* stream, int n, int d, const ff_fwd_args& a, int64_t
   return FF_OK;
 }
 
-int ff_wide_dispatch_fwd(int mode, void* stream, int n, int d, const ff_fwd_args& a) {
-  if (!ff_wide_supported(n, d)) {
-    ff_set_error("fused CNF kernels serve n <= 24 particles with n*d <= 60 in d = 2, 3");
-    return FF_EUNSUPPORTED;
-  }
+int ff_wide_dispatch_fwd(int mode, void* stream, int n, int d, const ff_fwd_args& a, const ff_plan& p) {
 #ifdef FF_WIDE_NO_FIN
   if (mode >= 2 && (a.fin.on & 2)) { ff_set_error("this build (FF_WIDE_NO_FIN) has no fused finish: ff_ode.compact_finish is not available"); return FF_EUNSUPPORTED; }
 #endif
-  if (mode == 0) { if (d == 2) launch_wide_flow<2, 0>(stream, a, n); else launch_wide_flow<3, 0>(stream, a, n); }
-  else if (mode == 1) { if (d == 2) launch_wide_flow<2, 1>(stream, a, n); else launch_wide_flow<3, 1>(stream, a, n); }
+  if (mode == 0) { if (d == 2) launch_wide_flow<2, 0>(stream, a, n, p); else launch_wide_flow<3, 0>(stream, a, n, p); }
+  else if (mode == 1) { if (d == 2) launch_wide_flow<2, 1>(stream, a, n, p); else launch_wide_flow<3, 1>(stream, a, n, p); }
   else {
-    const int T = (n * d + 4 + 15) / 16;
-#define FF_WE(D_, T_) if (d == D_ && T == T_) wide_with_fin(a, [&](auto fin) { launch_wide_eloc<D_, T_, decltype(fin)::value>(stream, a, n); });
+    const int T = p.param;
+#define FF_WE(D_, T_) if (d == D_ && T == T_) wide_with_fin(a, [&](auto fin) { launch_wide_eloc<D_, T_, decltype(fin)::value>(stream, a, n, p); });
     FF_WE(2, 1) FF_WE(2, 2) FF_WE(2, 3) FF_WE(2, 4) FF_WE(3, 1) FF_WE(3, 2) FF_WE(3, 3) FF_WE(3, 4)
 #undef FF_WE
   }

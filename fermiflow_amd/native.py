@@ -32,6 +32,19 @@ def set_kernel_family(family):
     return int(L.lib().ff_set_kernel_family(int(family)))
 
 
+PLAN_CALLS = ("flow", "flow_fb", "eloc", "eloc_fb", "adjoint", "adj_fb")                                   # FF_CALL_* (include/fermiflow.h)
+PLAN_FAMILIES = (None, "columns", "split", "rows", "mfma", "wide", "narrow", "tabulated", "direct")      # FF_FAMILY_*
+
+
+def kernel_plan(call, n, dim, cus=256):
+    """ff_kernel_plan: (family, walkers per group, walkers per round of the grid at `cus` compute units; 0: the grid never loops) of
+    the kernel the library's default routing gives `call` (one of PLAN_CALLS; "_fb": the direct kernel behind the table kernel) at
+    n particles in `dim` dimensions.  A pure function of its arguments: no GPU needed.  NotImplementedError for a shape no kernel serves."""
+    out = L.FFKernelPlanInfo()
+    L.check(L.lib().ff_kernel_plan(PLAN_CALLS.index(call), int(n), int(dim), L.i64(cus), C.byref(out)), "ff_kernel_plan")
+    return PLAN_FAMILIES[out.family], int(out.group), int(out.round)
+
+
 def set_sens_precision(bits):
     """ff_set_sens_precision: 64 (default) or 32 = single-precision sensitivity matrices in the matrix-core local-energy kernel
     (11 particles and more).  Returns the previous setting."""

@@ -168,6 +168,21 @@ const char* ff_last_error(void);
  * workgroup beyond (up to 24 particles, n d <= 60); 1 = one walker per workgroup for EVERY particle number (A/B and parity
  * testing; FF_WIDE=1 in the environment selects it at load time).  Returns the previous value. */
 int ff_set_kernel_family(int family);
+/* Which kernel this build's DEFAULT routing (no FF_ELOC_KERNEL, no forced family) gives a stand-alone call at (n, d), and the batch
+ * geometry of its launch: fermiflow_amd/csrc/ff_plan.h, the one place the dispatch itself reads.  call: the table kernel of the flow
+ * (ff_cnf_generate / ff_cnf_delta_logp), of the local energy (ff_eloc_nd: a persistent grid on a work queue) or of the adjoint, or
+ * the direct kernel launched behind each as its off-table fallback.  group: walkers a wave (a workgroup, FF_FAMILY_WIDE) takes at a
+ * time -- for the local energy the number that advance in lockstep.  round: walkers one round of the grid covers on a device of
+ * `cus` compute units; 0 where the grid is one workgroup per walker group and never loops.  A pure function: no environment
+ * variable is read and no GPU touched.  Returns 1 for a bad call id, cus < 1 or a null `out`, 2 for a shape no kernel serves. */
+enum { FF_CALL_FLOW = 0, FF_CALL_FLOW_FALLBACK, FF_CALL_ELOC, FF_CALL_ELOC_FALLBACK, FF_CALL_ADJOINT, FF_CALL_ADJOINT_FALLBACK };
+enum { FF_FAMILY_NONE = 0,
+       FF_FAMILY_COLUMNS, FF_FAMILY_SPLIT, FF_FAMILY_ROWS, FF_FAMILY_MFMA,      /* local energy, several walkers per wave */
+       FF_FAMILY_WIDE,                                                          /* every call: one walker per workgroup */
+       FF_FAMILY_NARROW,                                                        /* flow, several walkers per wave */
+       FF_FAMILY_TABULATED, FF_FAMILY_DIRECT };                                 /* adjoint, several walkers per wave */
+typedef struct ff_kernel_plan_info { int32_t family, group; int64_t round; } ff_kernel_plan_info;
+int ff_kernel_plan(int call, int n, int d, int64_t cus, ff_kernel_plan_info* out);
 /* Precision of the SENSITIVITY matrices of the local-energy pass in the one-walker-per-workgroup kernels (J = dz/dx with the
  * x-gradient of Delta, A = dv/dz, S = J J^T -- the operands of the two dense products per right-hand side): 64 (default) = fp64 on
  * v_mfma_f64_16x16x4_f64; 32 = fp32 on v_mfma_f32_16x16x4_f32 at twice the rate and half the registers ("fp32 MFMA path" of

@@ -226,76 +226,31 @@ def make_flow(eta, mu, dev):
     return ff.CNF(v, (0.0, 1.0))
 
 
-# ---- launch geometry of the persistent grids (fermiflow_amd/csrc), restated for the tests that must reach a second walker group
-# per workgroup.  Each family maps to (walkers per group, walkers per round of the grid); a round of None means one workgroup per
-# group (FF_GRID_CAP, ff_cnf_fwd.hip:1342): that grid never loops.  If a constant below drifts from the kernels the probe sets
-# become less targeted, but the tests built on them stay correct.
-FF_WAVE = 64
-ADJ_WPW = 2          # ff_cnf_adj.hip:213  FF_ADJ_WPW: waves per workgroup of the tabulated adjoint, each with its own walker groups
-ADJ_G12 = 3          # ff_cnf_adj.hip:220  FF_ADJ_G12: walkers per wave of the tabulated adjoint at n d = 12
-MFMA_WPS = 2         # ff_cnf_fwd.hip FF_MFMA_WPS: the matrix-core kernel's cap is this many times the persistent grid of fwd_grid()
-FWD_FB_GRID = 2048   # ff_cnf_fwd.hip:1487 grid-stride cap of the direct fallback behind a flow table kernel
-ROWS_SPLIT = {1: 1, 2: 1, 3: 1, 4: 1, 5: 1, 6: 1, 7: 2, 8: 2, 9: 3, 10: 3, 11: 2, 12: 2}   # ff_cnf_fwd.hip:1581 FF_RW
-
-
+# ---- launch geometry of the persistent grids, for the tests that must reach a second walker group per workgroup: read from the
+# library's own plan (ff_kernel_plan, fermiflow_amd/csrc/ff_plan.h -- what the dispatch itself switches on).  Each family maps to
+# (walkers per group, walkers per round of the grid); a round of None means one workgroup per group: that grid never loops.
 def cu_count(hostsim=False):
     """Compute units the grid caps are sized by: the device's, or the host simulator's 2 (tests/hostsim/hip_shim.h:85)."""
     return 2 if hostsim else torch.cuda.get_device_properties(0).multi_processor_count
 
 
-def _geom_G(n, d):      # ff_ode.h ff_geom_G = ff_geom<N, D>::G: walkers per wave of the narrow kernels
-    M = n * d
-    return min(16, FF_WAVE // M)
-
-
-def _adjtab_G(n, d):    # ff_cnf_adj.hip:227 ff_adjtab_G
-    M = n * d
-    g = min(16, FF_WAVE // M)
-    if M == 12:
-        return ADJ_G12
-    if d == 2 and n in (4, 5, 7, 9, 10, 11):
-        return max(1, min(FF_WAVE // (n * (n + 1) // 2), g))
-    return g
-
-
-def _narrow(n, d):      # ff_ode.h ff_narrow_shape: the shapes of FF_NARROW_COLUMNS and FF_NARROW_ROWS_ONLY
-    return (d == 2 and 1 <= n <= 12) or (d == 3 and 2 <= n <= 4)
+_FAMILY_NAMES = {"flow": {"narrow": "flow_table", "wide": "flow_wide"}, "flow_fb": {"narrow": "flow_direct_fb", "wide": "flow_wide"},
+                 "adjoint": {"tabulated": "adj_tab", "wide": "adj_wide"}, "adj_fb": {"direct": "adj_direct", "wide": "adj_wide"}}
 
 
 def kernel_families(call, n, d, cus, hostsim=False):
     """{family: (walkers per group, walkers per round or None)} of the kernels that do the work of one stand-alone native call
     with a radial-table net and every radius on the table: call = "flow" (cnf_generate / cnf_delta_logp), "eloc" (ff_eloc_nd,
     queue mode), "adjoint"; "flow_fb", "eloc_fb", "adj_fb" = the direct kernels that redo the call when a radius is off the table.
-    The host simulator builds with FF_MFMA_FROM=99 (tests/hostsim/Makefile): no matrix-core local-energy kernel there."""
-    q = 4 * cus                                     # ff_cnf_fwd.hip fwd_grid(), ff_cnf_adj.hip adj_grid(): four waves per CU (ff_api.hip ff_device_cus)
-    if call in ("flow", "flow_fb"):
-        if not _narrow(n, d):                       # ff_wide.hip:1020 launch_wide_flow: one walker per workgroup, 64 per CU
-            return {"flow_wide": (1, 64 * cus)}
-        G = _geom_G(n, d)
-        return {"flow_table": (G, None)} if call == "flow" else {"flow_direct_fb": (G, FWD_FB_GRID * G)}   # ff_cnf_fwd.hip:1478, 1487
-    if call in ("adjoint", "adj_fb"):
-        if not _narrow(n, d):                       # ff_cnf_adj.hip:953: one walker per workgroup
-            return {"adj_wide": (1, q)}
-        if call == "adj_fb":                        # ff_cnf_adj.hip:834 launch_adj: G walkers per single-wave workgroup
-            return {"adj_direct": (_geom_G(n, d), q * _geom_G(n, d))}
-        Gt = _adjtab_G(n, d)                        # ff_cnf_adj.hip:961: G walkers per wave, ADJ_WPW waves per workgroup
-        return {"adj_tab": (Gt, q * ADJ_WPW * Gt)}
-    assert call in ("eloc", "eloc_fb"), call
-    M = n * d
-    if not _narrow(n, d) or (d == 2 and n >= 11):   # ff_cnf_fwd.hip:1579 (wide_from = 11); ff_wide.hip:1027 launch_wide_eloc
-        T = (M + 4 + 15) // 16
-        per_cu = 1 if T >= 3 else (2 if T == 2 else 4)
-        return {"eloc_wide": (1, per_cu * cus)}
-    if d == 2 and 4 <= n <= 6 and not hostsim:      # ff_cnf_fwd.hip:1521 launch_mfma: four walkers per wave
-        return {"eloc_mfma": (4, (MFMA_WPS if call == "eloc" else 1) * q * 4)}
-    if d == 3 or n in (1, 7, 9, 10, 11):            # ff_ode.h ff_narrow_rows_only (and n = 10: FF_RW), ff_cnf_fwd.hip launch_rows
-        G = min(16, FF_WAVE // (M * (ROWS_SPLIT[n] if d == 2 else 1)))
-        return {"eloc_rows": (G, q * G)}
-    if n == 8:                                      # ff_cnf_fwd.hip:1495 launch_split
-        G = FF_WAVE // (2 * M)
-        return {"eloc_split": (G, q * G)}
-    G = _geom_G(n, d)                               # ff_cnf_fwd.hip:1475 launch_fwd (column sweep, n = 2, 3)
-    return {"eloc_columns": (G, q * G)}
+    hostsim: the plan of the host simulator's build (FF_MFMA_FROM=99, tests/hostsim/Makefile: no matrix-core kernel there)."""
+    from fermiflow_amd import native
+    if hostsim:
+        from tests.hostsim import simlib
+        fam, g, r = simlib.kernel_plan(native.PLAN_CALLS.index(call), n, d, cus)
+        fam = native.PLAN_FAMILIES[fam]
+    else:
+        fam, g, r = native.kernel_plan(call, n, d, cus)
+    return {"eloc_" + fam if call in ("eloc", "eloc_fb") else _FAMILY_NAMES[call][fam]: (g, r or None)}
 
 
 def looping_batch(fams, rounds=2):

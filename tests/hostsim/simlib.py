@@ -26,6 +26,10 @@ class FFOde(C.Structure):
                 ("compact_finish", C.c_int32), ("after_main_event", C.c_void_p), ("walker_h_equal", C.c_int32)]
 
 
+class FFKernelPlanInfo(C.Structure):
+    _fields_ = [("family", C.c_int32), ("group", C.c_int32), ("round", C.c_int64)]
+
+
 def build():
     subprocess.check_call(["make", "-s", "-j4", "-C", HERE])
 
@@ -45,6 +49,13 @@ def lib():
         _LIB.ff_eloc_workspace_bytes.restype = C.c_size_t
         _LIB.ff_cnf_adjoint_workspace_bytes.restype = C.c_size_t
     return _LIB
+
+
+def kernel_plan(call, n, d, cus):
+    """ff_kernel_plan of the simulator's build: (FF_FAMILY_* id, walkers per group, walkers per round) of call id FF_CALL_*"""
+    out = FFKernelPlanInfo()
+    _ck(lib().ff_kernel_plan(call, n, d, C.c_int64(cus), C.byref(out)))
+    return out.family, out.group, out.round
 
 
 def _d(a):

@@ -453,3 +453,313 @@ def test_argument_refusals_keep_their_status_and_text():
     refused(1, "ff_eloc: null orbital table", "ff_eloc", B, 13, 3, None, p8, *spins["ff_eloc"][1]())
     refused(1, "ff_eloc: bad particle numbers or dimension", "ff_eloc_nd", B, 3, 3, 4, p8, p8, *spins["ff_eloc_nd"][1]())
     refused(2, "ff_eloc_finish3d: walker too large", "ff_eloc_finish3d", B, 11, 11, p8, p8, *spins["ff_eloc_finish3d"][1]())      # 3 n > 64
+
+
+# What tests/common.py kernel_families returned before it read ff_kernel_plan -- a Python restatement of the dispatch of csrc/, checked
+# against the C++ shape by shape when it was retired -- for all six calls at every supported shape: data, not a second implementation.
+PLAN_TABLE = {      # (call, n, d): (family, walkers per group, walkers per round at 2 CUs, at 256 CUs)
+    ('flow', 1, 2): ('flow_table', 16, None, None),
+    ('flow', 2, 2): ('flow_table', 16, None, None),
+    ('flow', 3, 2): ('flow_table', 10, None, None),
+    ('flow', 4, 2): ('flow_table', 8, None, None),
+    ('flow', 5, 2): ('flow_table', 6, None, None),
+    ('flow', 6, 2): ('flow_table', 5, None, None),
+    ('flow', 7, 2): ('flow_table', 4, None, None),
+    ('flow', 8, 2): ('flow_table', 4, None, None),
+    ('flow', 9, 2): ('flow_table', 3, None, None),
+    ('flow', 10, 2): ('flow_table', 3, None, None),
+    ('flow', 11, 2): ('flow_table', 2, None, None),
+    ('flow', 12, 2): ('flow_table', 2, None, None),
+    ('flow', 13, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 14, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 15, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 16, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 17, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 18, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 19, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 20, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 21, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 22, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 23, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 24, 2): ('flow_wide', 1, 128, 16384),
+    ('flow', 1, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 2, 3): ('flow_table', 10, None, None),
+    ('flow', 3, 3): ('flow_table', 7, None, None),
+    ('flow', 4, 3): ('flow_table', 5, None, None),
+    ('flow', 5, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 6, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 7, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 8, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 9, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 10, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 11, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 12, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 13, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 14, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 15, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 16, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 17, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 18, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 19, 3): ('flow_wide', 1, 128, 16384),
+    ('flow', 20, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 1, 2): ('flow_direct_fb', 16, 32768, 32768),
+    ('flow_fb', 2, 2): ('flow_direct_fb', 16, 32768, 32768),
+    ('flow_fb', 3, 2): ('flow_direct_fb', 10, 20480, 20480),
+    ('flow_fb', 4, 2): ('flow_direct_fb', 8, 16384, 16384),
+    ('flow_fb', 5, 2): ('flow_direct_fb', 6, 12288, 12288),
+    ('flow_fb', 6, 2): ('flow_direct_fb', 5, 10240, 10240),
+    ('flow_fb', 7, 2): ('flow_direct_fb', 4, 8192, 8192),
+    ('flow_fb', 8, 2): ('flow_direct_fb', 4, 8192, 8192),
+    ('flow_fb', 9, 2): ('flow_direct_fb', 3, 6144, 6144),
+    ('flow_fb', 10, 2): ('flow_direct_fb', 3, 6144, 6144),
+    ('flow_fb', 11, 2): ('flow_direct_fb', 2, 4096, 4096),
+    ('flow_fb', 12, 2): ('flow_direct_fb', 2, 4096, 4096),
+    ('flow_fb', 13, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 14, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 15, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 16, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 17, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 18, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 19, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 20, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 21, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 22, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 23, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 24, 2): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 1, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 2, 3): ('flow_direct_fb', 10, 20480, 20480),
+    ('flow_fb', 3, 3): ('flow_direct_fb', 7, 14336, 14336),
+    ('flow_fb', 4, 3): ('flow_direct_fb', 5, 10240, 10240),
+    ('flow_fb', 5, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 6, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 7, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 8, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 9, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 10, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 11, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 12, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 13, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 14, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 15, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 16, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 17, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 18, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 19, 3): ('flow_wide', 1, 128, 16384),
+    ('flow_fb', 20, 3): ('flow_wide', 1, 128, 16384),
+    ('eloc', 1, 2): ('eloc_rows', 16, 128, 16384),
+    ('eloc', 2, 2): ('eloc_columns', 16, 128, 16384),
+    ('eloc', 3, 2): ('eloc_columns', 10, 80, 10240),
+    ('eloc', 4, 2): ('eloc_mfma', 4, 64, 8192),
+    ('eloc', 5, 2): ('eloc_mfma', 4, 64, 8192),
+    ('eloc', 6, 2): ('eloc_mfma', 4, 64, 8192),
+    ('eloc', 7, 2): ('eloc_rows', 2, 16, 2048),
+    ('eloc', 8, 2): ('eloc_split', 2, 16, 2048),
+    ('eloc', 9, 2): ('eloc_rows', 1, 8, 1024),
+    ('eloc', 10, 2): ('eloc_rows', 1, 8, 1024),
+    ('eloc', 11, 2): ('eloc_wide', 1, 4, 512),
+    ('eloc', 12, 2): ('eloc_wide', 1, 4, 512),
+    ('eloc', 13, 2): ('eloc_wide', 1, 4, 512),
+    ('eloc', 14, 2): ('eloc_wide', 1, 4, 512),
+    ('eloc', 15, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 16, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 17, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 18, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 19, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 20, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 21, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 22, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 23, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 24, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc', 1, 3): ('eloc_wide', 1, 8, 1024),
+    ('eloc', 2, 3): ('eloc_rows', 10, 80, 10240),
+    ('eloc', 3, 3): ('eloc_rows', 7, 56, 7168),
+    ('eloc', 4, 3): ('eloc_rows', 5, 40, 5120),
+    ('eloc', 5, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc', 6, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc', 7, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc', 8, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc', 9, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc', 10, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 11, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 12, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 13, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 14, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 15, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 16, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 17, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 18, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 19, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc', 20, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 1, 2): ('eloc_rows', 16, 128, 16384),
+    ('eloc_fb', 2, 2): ('eloc_columns', 16, 128, 16384),
+    ('eloc_fb', 3, 2): ('eloc_columns', 10, 80, 10240),
+    ('eloc_fb', 4, 2): ('eloc_mfma', 4, 32, 4096),
+    ('eloc_fb', 5, 2): ('eloc_mfma', 4, 32, 4096),
+    ('eloc_fb', 6, 2): ('eloc_mfma', 4, 32, 4096),
+    ('eloc_fb', 7, 2): ('eloc_rows', 2, 16, 2048),
+    ('eloc_fb', 8, 2): ('eloc_split', 2, 16, 2048),
+    ('eloc_fb', 9, 2): ('eloc_rows', 1, 8, 1024),
+    ('eloc_fb', 10, 2): ('eloc_rows', 1, 8, 1024),
+    ('eloc_fb', 11, 2): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 12, 2): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 13, 2): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 14, 2): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 15, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 16, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 17, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 18, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 19, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 20, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 21, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 22, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 23, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 24, 2): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 1, 3): ('eloc_wide', 1, 8, 1024),
+    ('eloc_fb', 2, 3): ('eloc_rows', 10, 80, 10240),
+    ('eloc_fb', 3, 3): ('eloc_rows', 7, 56, 7168),
+    ('eloc_fb', 4, 3): ('eloc_rows', 5, 40, 5120),
+    ('eloc_fb', 5, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 6, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 7, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 8, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 9, 3): ('eloc_wide', 1, 4, 512),
+    ('eloc_fb', 10, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 11, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 12, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 13, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 14, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 15, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 16, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 17, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 18, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 19, 3): ('eloc_wide', 1, 2, 256),
+    ('eloc_fb', 20, 3): ('eloc_wide', 1, 2, 256),
+    ('adjoint', 1, 2): ('adj_tab', 16, 256, 32768),
+    ('adjoint', 2, 2): ('adj_tab', 16, 256, 32768),
+    ('adjoint', 3, 2): ('adj_tab', 10, 160, 20480),
+    ('adjoint', 4, 2): ('adj_tab', 6, 96, 12288),
+    ('adjoint', 5, 2): ('adj_tab', 4, 64, 8192),
+    ('adjoint', 6, 2): ('adj_tab', 3, 48, 6144),
+    ('adjoint', 7, 2): ('adj_tab', 2, 32, 4096),
+    ('adjoint', 8, 2): ('adj_tab', 4, 64, 8192),
+    ('adjoint', 9, 2): ('adj_tab', 1, 16, 2048),
+    ('adjoint', 10, 2): ('adj_tab', 1, 16, 2048),
+    ('adjoint', 11, 2): ('adj_tab', 1, 16, 2048),
+    ('adjoint', 12, 2): ('adj_tab', 2, 32, 4096),
+    ('adjoint', 13, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 14, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 15, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 16, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 17, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 18, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 19, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 20, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 21, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 22, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 23, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 24, 2): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 1, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 2, 3): ('adj_tab', 10, 160, 20480),
+    ('adjoint', 3, 3): ('adj_tab', 7, 112, 14336),
+    ('adjoint', 4, 3): ('adj_tab', 3, 48, 6144),
+    ('adjoint', 5, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 6, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 7, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 8, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 9, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 10, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 11, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 12, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 13, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 14, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 15, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 16, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 17, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 18, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 19, 3): ('adj_wide', 1, 8, 1024),
+    ('adjoint', 20, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 1, 2): ('adj_direct', 16, 128, 16384),
+    ('adj_fb', 2, 2): ('adj_direct', 16, 128, 16384),
+    ('adj_fb', 3, 2): ('adj_direct', 10, 80, 10240),
+    ('adj_fb', 4, 2): ('adj_direct', 8, 64, 8192),
+    ('adj_fb', 5, 2): ('adj_direct', 6, 48, 6144),
+    ('adj_fb', 6, 2): ('adj_direct', 5, 40, 5120),
+    ('adj_fb', 7, 2): ('adj_direct', 4, 32, 4096),
+    ('adj_fb', 8, 2): ('adj_direct', 4, 32, 4096),
+    ('adj_fb', 9, 2): ('adj_direct', 3, 24, 3072),
+    ('adj_fb', 10, 2): ('adj_direct', 3, 24, 3072),
+    ('adj_fb', 11, 2): ('adj_direct', 2, 16, 2048),
+    ('adj_fb', 12, 2): ('adj_direct', 2, 16, 2048),
+    ('adj_fb', 13, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 14, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 15, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 16, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 17, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 18, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 19, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 20, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 21, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 22, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 23, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 24, 2): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 1, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 2, 3): ('adj_direct', 10, 80, 10240),
+    ('adj_fb', 3, 3): ('adj_direct', 7, 56, 7168),
+    ('adj_fb', 4, 3): ('adj_direct', 5, 40, 5120),
+    ('adj_fb', 5, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 6, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 7, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 8, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 9, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 10, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 11, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 12, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 13, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 14, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 15, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 16, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 17, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 18, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 19, 3): ('adj_wide', 1, 8, 1024),
+    ('adj_fb', 20, 3): ('adj_wide', 1, 8, 1024),
+}
+PLAN_TABLE_SIM = {**PLAN_TABLE,      # the host simulator's build (FF_MFMA_FROM=99): no matrix-core kernel
+    ('eloc', 4, 2): ('eloc_columns', 8, 64, 8192),
+    ('eloc', 5, 2): ('eloc_columns', 6, 48, 6144),
+    ('eloc', 6, 2): ('eloc_columns', 5, 40, 5120),
+    ('eloc_fb', 4, 2): ('eloc_columns', 8, 64, 8192),
+    ('eloc_fb', 5, 2): ('eloc_columns', 6, 48, 6144),
+    ('eloc_fb', 6, 2): ('eloc_columns', 5, 40, 5120),
+}
+# walkers the sweep's shrink threshold was computed for before VMC._init_sweep read the plan: n = 1..24 in d = 2, n = 1..20 in d = 3
+H_SHRINK_G = {2: [16, 16, 10, 4, 4, 4, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1],
+              3: [21, 10, 7, 5, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1]}
+
+
+def test_kernel_plan_reproduces_the_recorded_routing():
+    """ff_kernel_plan (csrc/ff_plan.h: what the dispatch switches on) of the GPU build and of the simulator's build gives, at every
+    supported shape and for every call, the family, group size and round the recorded table holds, at 2 and at 256 compute units;
+    shapes beyond the kernels are refused.  The sweep's shrink threshold follows the plan's lockstep count: unchanged at every shape
+    but one particle in d = 3, which the one-walker-per-workgroup kernel serves (0.25; the retired formula took it for 21 walkers)."""
+    from fermiflow_amd import native
+    from fermiflow_amd.VMC import _Sweep
+    from tests.common import kernel_families
+    shapes = [(n, 2) for n in range(1, 25)] + [(n, 3) for n in range(1, 21)]
+    assert set(PLAN_TABLE) == set(PLAN_TABLE_SIM) == {(c, n, d) for c in native.PLAN_CALLS for n, d in shapes}
+    for hostsim, table in ((False, PLAN_TABLE), (True, PLAN_TABLE_SIM)):
+        for (call, n, d), (family, group, r2, r256) in table.items():
+            for cus, rnd in ((2, r2), (256, r256)):
+                assert kernel_families(call, n, d, cus, hostsim=hostsim) == {family: (group, rnd)}, (hostsim, call, n, d, cus)
+    for call in native.PLAN_CALLS:
+        for n, d in ((0, 2), (25, 2), (21, 3), (6, 4), (6, 1)):
+            with pytest.raises(NotImplementedError):
+                native.kernel_plan(call, n, d)
+    with pytest.raises(ValueError):
+        native.kernel_plan("eloc", 6, 2, cus=0)
+    for n, d in shapes:
+        s = _Sweep()
+        s._init_sweep(n, d)
+        G = H_SHRINK_G[d][n - 1]
+        want = 0.25 if (n, d) == (1, 3) else min(0.25, max(0.06, 1.0 - 0.65 ** (1.0 / G)))
+        assert s._h_shrink_at == want, (n, d, s._h_shrink_at, want)
+        assert G == PLAN_TABLE[("eloc", n, d)][1] or (n, d) == (1, 3)
