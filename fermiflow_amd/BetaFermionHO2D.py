@@ -10,11 +10,11 @@ import time
 
 import torch
 
-from . import HO2D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, BetaVMC, Observables, checkpoint
+from . import HO2D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, BetaVMC, Observables, checkpoint, frames
 from .utils import make_adam
 
 
-def main(argv=None):
+def build_parser():
     import argparse
     parser = argparse.ArgumentParser(description="Finite-temperature variational Monte Carlo simulation")
     parser.add_argument("--beta", type=float, default=2.0, help="inverse temperature")
@@ -37,7 +37,14 @@ def main(argv=None):
                         help=".npz file for the radial densities and pair-distance distributions averaged over the run's iterations")
     parser.add_argument("--observe_rmax", type=float, default=6.0, help="largest radius / distance of the observables' histograms")
     parser.add_argument("--observe_bins", type=int, default=240, help="number of bins of the observables' histograms")
+    frames.add_arguments(parser)
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
+    frames.check_arguments(parser, args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -88,6 +95,10 @@ def main(argv=None):
         model.observables.all_reduce_()
         if rank == 0:
             model.observables.save_npz(args.observe_out)
+    if args.frames_out:
+        zx = model._sample_on_root((args.frames_batch,), nframes=args.nframes)      # (every rank: the state list is broadcast)
+        if rank == 0:
+            frames.save_npz(args.frames_out, zx[1], cnf.t_span, args.nup, args.ndown, 2)
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -14,11 +14,11 @@ import time
 
 import torch
 
-from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, Observables, checkpoint, native
+from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, Observables, checkpoint, frames, native
 from .utils import make_adam
 
 
-def main(argv=None):
+def build_parser():
     import argparse
     parser = argparse.ArgumentParser(description="Ground-state variational Monte Carlo simulation")
     parser.add_argument("--nup", type=int, default=6, help="number of spin-up electrons")
@@ -41,7 +41,14 @@ def main(argv=None):
                         help=".npz file for the radial densities and pair-distance distributions averaged over the run's iterations")
     parser.add_argument("--observe_rmax", type=float, default=6.0, help="largest radius / distance of the observables' histograms")
     parser.add_argument("--observe_bins", type=int, default=240, help="number of bins of the observables' histograms")
+    frames.add_arguments(parser)
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
+    frames.check_arguments(parser, args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -92,6 +99,9 @@ def main(argv=None):
         model.observables.all_reduce_()
         if rank == 0:
             model.observables.save_npz(args.observe_out)
+    if args.frames_out and rank == 0:
+        z = basedist.sample(model.orbitals_up, model.orbitals_down, (args.frames_batch,))
+        frames.save_npz(args.frames_out, cnf.generate(z, nframes=args.nframes), cnf.t_span, args.nup, args.ndown, args.dim)
     if world > 1:
         torch.distributed.destroy_process_group()
 

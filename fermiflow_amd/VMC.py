@@ -682,9 +682,10 @@ class BetaVMC(_Sweep, torch.nn.Module):
         D.broadcast_(idx)
         return idx
 
-    def _set_shard(self, idx_global):
+    def _set_shard(self, idx_global, whole=False):
+        """This rank's block of the global state list (whole: all of it, for a batch that one rank draws alone)."""
         rank, world = D.world()
-        off, cnt = D.shard(idx_global.numel(), rank, world)
+        off, cnt = (0, idx_global.numel()) if whole else D.shard(idx_global.numel(), rank, world)
         self._ws = idx_global[off:off + cnt].to(device=self.basedist.device, dtype=torch.int32).contiguous()
         self._coll = None
         self._nglobal = idx_global.numel()
@@ -701,6 +702,18 @@ class BetaVMC(_Sweep, torch.nn.Module):
         z = self._sample_base(cnt)
         x = self.cnf.generate(z, nframes=nframes)
         return z, x
+
+    def _sample_on_root(self, sample_shape, nframes=None):
+        """sample() of the WHOLE batch on rank 0 alone (the driver's --frames_out, after the last iteration).  Every rank calls it
+        -- the state list is drawn by rank 0 and broadcast -- and rank 0 returns (z, x), the others None."""
+        batch = 1
+        for s in sample_shape:
+            batch *= int(s)
+        idx = self._draw_states(batch)
+        if D.world()[0] != 0:
+            return None
+        z = self._sample_base(self._set_shard(idx, whole=True))
+        return z, self.cnf.generate(z, nframes=nframes)
 
     def _sample_base(self, cnt):
         from .base_dist import _draw_seed

@@ -1,6 +1,7 @@
 // ff_cnf_fwd.hip -- fused forward CNF integrations:
 //   MODE 0  CNF.generate      (src/flow.py:42-44)     state z                      heads eta
 //   MODE 1  CNF.delta_logp    (src/flow.py:51-55)     state (z, Delta)             heads eta, eta'
+//   FF_MODE_FRAMES  CNF.generate(z, nframes) (src/flow.py:45-48): MODE 0 that lands on every frame time and writes the frame
 //   MODE 2  local-energy pass (src/VMC.py:46-49, replaces the 2+2*n*d nested adjoint solves of
 //           src/utils.py:40-65)  state (z, J = dz/dx, kbar = lap_x z, Delta, grad_x Delta, lap_x Delta)
 //                                                                                heads eta .. eta'''
@@ -63,9 +64,12 @@
 #ifndef FF_FWD_STATIC
 #define FF_FWD_STATIC(N, D, MODE, TAB) ((MODE) == 0 && (TAB) && (N) * (D) <= 12)
 #endif
-template <int N, int D, int MODE, bool TAB>
-__global__ void __launch_bounds__(FF_WAVE, (MODE == 0 && TAB && N * D <= 12) ? FF_FLOW_WAVES : FF_FWD_WAVES_PER_SIMD)
+template <int N, int D, int MODE_, bool TAB>
+__global__ void __launch_bounds__(FF_WAVE, ((MODE_ == 0 || MODE_ == FF_MODE_FRAMES) && TAB && N * D <= 12) ? FF_FLOW_WAVES : FF_FWD_WAVES_PER_SIMD)
 ff_ode_fwd_kernel(ff_fwd_args A) {
+  // FF_MODE_FRAMES is MODE 0 in everything but its stepper and its writes (ff_frame_stepper)
+  constexpr bool FRAMES = MODE_ == FF_MODE_FRAMES;
+  constexpr int MODE = FRAMES ? 0 : MODE_;
   if constexpr (MODE == 0) FF_SETPRIO();      // the flow pass runs beside the tail of the prefetched sampler (ff_common.h)
   using Gm = ff_geom<N, D>;
   constexpr int M = Gm::M, G = Gm::G, P = Gm::P, R = Gm::RA;
@@ -201,8 +205,13 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
 #pragma unroll
       for (int k = 0; k < M; k++) y[1 + k] = (k == i) ? 1.0 : 0.0;
     }
-    ff_stepper S;
-    S.begin(A.ta, A.tb, valid);
+    std::conditional_t<FRAMES, ff_frame_stepper, ff_stepper> S;
+    if constexpr (FRAMES) {
+      S.begin(A.ta, A.tb, valid, A.nframes);
+      if (valid) A.y_out[b * M + i] = y[0];   // frame 0
+    } else {
+      S.begin(A.ta, A.tb, valid);
+    }
     // warm start (ff_ode.walker_h_init): the step size to try first, instead of the probe evaluation of the Hairer start
     // (local-energy pass) walkers of a low cost class: looser tolerance for the sensitivity components, larger first step
     const bool loose = MODE == 2 && ff_opt_load(A.wclass, valid, b, A.y_in, (int32_t)0x7fffffff) <= A.sens_class;
@@ -572,6 +581,9 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
 #pragma unroll
           for (int v = 0; v < NV; v++) { y[v] = in[v]; c0[v] = out[v]; }
         }
+        if constexpr (FRAMES) {   // the step ended on a frame: the lane-to-address mapping of the final write of y_out
+          if (valid && S.landed >= 0) A.y_out[((int64_t)S.landed * A.B + b) * M + i] = y[0];
+        }
         S.plan();
         // wave-wide: anybody still integrating?  anybody rejected (then everyone passes through stage 0)?
         const int any = ff_wave_or(&s_any, lane, S.done ? 0 : ((was_active && !acc) ? 3 : 1));
@@ -619,7 +631,11 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
 #else
       const double bad = failed ? __builtin_nan("") : 0.0;
 #endif
-      A.y_out[b * M + i] = y[0] + bad;
+      if constexpr (FRAMES) {   // the frames the walker did not reach: NaN after a failure (an empty interval: the state itself)
+        for (int k = S.kf; k < A.nframes; k++) A.y_out[((int64_t)k * A.B + b) * M + i] = y[0] + bad;
+      } else {
+        A.y_out[b * M + i] = y[0] + bad;
+      }
       if constexpr (MODE >= 1) { if (i == 0) A.dl_out[b] = y[IDL] + bad; }
       if constexpr (MODE == 2) {
 #pragma unroll
@@ -1611,6 +1627,26 @@ int ff_cnf_generate(void* stream, int64_t B, int n, int d, const ff_net* net, co
   ff_fill_common(a, B, net, ode, true);
   a.y_in = z; a.y_out = x_out; a.stats = stats;
   return dispatch_fwd<0>(stream, n, d, a);
+}
+
+int ff_cnf_generate_frames(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* z,
+                           int nframes, double* frames, int32_t* stats) {
+  if (const int st = ff_check_flow("ff_cnf_generate_frames", B >= 0 && n > 0 && d > 0 && nframes >= 1, net, ode)) return st;
+  FF_CHECK(z && frames, FF_EINVAL, "ff_cnf_generate_frames: null pointer");
+  if (ff_plan_flow(n, d, false, fwd_knobs()).family == FF_FAMILY_NONE)
+    return ff_refuse(FF_EUNSUPPORTED, "ff_cnf_generate_frames", "fused CNF kernels serve n <= 24 particles with n*d <= 60 in d = 2, 3");
+  if (B == 0) return FF_OK;
+  if (nframes == 1) {      // the frame at t0 alone: nothing to integrate
+    if (hipMemcpyAsync(frames, z, sizeof(double) * (size_t)B * (size_t)(n * d), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+      ff_set_error("ff_cnf_generate_frames: copy of frame 0 failed");
+      return FF_ELAUNCH;
+    }
+    return FF_OK;
+  }
+  ff_fwd_args a = {};
+  ff_fill_common(a, B, net, ode, true);
+  a.y_in = z; a.y_out = frames; a.nframes = nframes; a.stats = stats;
+  return dispatch_fwd<FF_MODE_FRAMES>(stream, n, d, a);
 }
 
 int ff_cnf_delta_logp(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* x,

@@ -42,9 +42,16 @@ struct ff_dp5_ctl {
 
 // Consumes out = f(stage input of stage s).  wgt(v): weight of component v in the error norm; gsum(part): the sum of a
 // per-lane partial over the workgroup (identical on all lanes).  Returns the next stage, or 99 when the walker is done.
-// c3 is any indexable per-lane vector (registers, or lane-private LDS columns).
-template <int NV, class C3, class W, class G>
-FF_D int ff_dp5_consume(int s, ff_stepper& S, ff_dp5_ctl& C, double* y, double* c0, double* c1, double* c2, C3& c3,
+// c3 is any indexable per-lane vector (registers, or lane-private LDS columns).  S: ff_stepper, or ff_frame_stepper (ff_ode.h).
+// PIN_B: which product of the sum B0 k0 + B2 k2 + B3 k3 of the candidate y_new stays a multiplication when the compiler contracts the
+// sum into fused multiply-adds (-ffp-contract=fast).  0: the compiler's choice -- every kernel but the frame-writing ones; it differs
+// from instantiation to instantiation (hipcc 7.2: B2's in ff_wide_flow_kernel<D, 0, true>, B0's in <D, 0, false>), which is one
+// rounding of y_new.  1 / 2: B2's / B0's, written out: the frame-writing instantiation of a kernel takes its mode-0 twin's, so that
+// its integration is that kernel's bit for bit (tests/test_gpu_frames.py::test_frame_zero_and_two_frames).
+// tools/check_frames_contraction.py reads the choice of every flow kernel off the built library and compares each frame-writing
+// kernel with its twin (tests/test_frames_host.py runs it): after a toolchain update its report says which value belongs here.
+template <int NV, int PIN_B = 0, class ST, class C3, class W, class G>
+FF_D int ff_dp5_consume(int s, ST& S, ff_dp5_ctl& C, double* y, double* c0, double* c1, double* c2, C3& c3,
                         const double* out, W wgt, G gsum) {
   const double h = S.h, rtol = C.rtol, atol = C.atol;
   if (s == -2) {
@@ -100,7 +107,9 @@ FF_D int ff_dp5_consume(int s, ff_stepper& S, ff_dp5_ctl& C, double* y, double* 
       const double k0v = c0[v], k1v = c1[v], k2v = c2[v], k3v = out[v], yv = y[v];
       c0[v] = fma(h, FF_A40 * k0v + FF_A41 * k1v + FF_A42 * k2v + FF_A43 * k3v, yv);
       c1[v] = fma(h, FF_A50 * k0v + FF_A51 * k1v + FF_A52 * k2v + FF_A53 * k3v, yv);
-      c2[v] = fma(h, FF_B0 * k0v + FF_B2 * k2v + FF_B3 * k3v, yv);
+      if constexpr (PIN_B == 1) c2[v] = fma(h, fma(FF_B3, k3v, fma(FF_B0, k0v, FF_B2 * k2v)), yv);
+      else if constexpr (PIN_B == 2) c2[v] = fma(h, fma(FF_B3, k3v, fma(FF_B2, k2v, FF_B0 * k0v)), yv);
+      else c2[v] = fma(h, FF_B0 * k0v + FF_B2 * k2v + FF_B3 * k3v, yv);
       c3[v] = h * (FF_E0 * k0v + FF_E2 * k2v + FF_E3 * k3v);
     }
     return 4;

@@ -4,13 +4,18 @@
 #include "ff_common.h"
 #include "ff_plan.h"
 
+// MODE of the two flow kernels (ff_ode_fwd_kernel, ff_wide_flow_kernel): 0 CNF.generate, 1 CNF.delta_logp, 2 local-energy
+// sensitivities, FF_MODE_FRAMES CNF.generate(z, nframes) -- the integration of MODE 0 that writes every frame it lands on
+#define FF_MODE_FRAMES 3
+
 struct ff_fwd_args {
   int64_t B;
   ff_net net;
   double ta, tb, rtol, atol;
   int max_steps;
+  int nframes;          // FF_MODE_FRAMES: frames of the trajectory, >= 2 (in the padding behind max_steps: no offset of this struct moves)
   const double* y_in;   // (B, M)
-  double* y_out;        // (B, M)   z(tb)
+  double* y_out;        // (B, M)   z(tb); FF_MODE_FRAMES: (nframes, B, M), frame k = z(ta + k (tb - ta) / (nframes - 1))
   double* dl_out;       // (B)      Delta(tb)                  MODE >= 1
   double* Jt;           // (B, M, M) Jt[b][i][k] = dz_k/dx_i   MODE 2
   double* kbar;         // (B, M)
@@ -57,7 +62,7 @@ struct ff_fwd_args {
 };
 
 // Kernels for walkers that do not fit one wave's column / row layouts (n > 12 in d = 2, n > 4 in d = 3): ff_wide.hip.
-// mode: 0 CNF.generate, 1 CNF.delta_logp, 2 local-energy sensitivities.  Returns FF_OK / FF_EUNSUPPORTED / FF_ELAUNCH.
+// mode: 0 CNF.generate, 1 CNF.delta_logp, 2 local-energy sensitivities, FF_MODE_FRAMES.  Returns FF_OK / FF_EUNSUPPORTED / FF_ELAUNCH.
 // p: the plan that chose the family (ff_plan_flow / ff_plan_eloc, FF_FAMILY_WIDE): its grid cap and, for mode 2, T = p.param
 int ff_wide_dispatch_fwd(int mode, void* stream, int n, int d, const ff_fwd_args& a, const ff_plan& p);
 // the local-energy kernel of the family for the walkers a launch with heavy_mode = 1 selects: at most `max_groups` single-walker workgroups

@@ -11,6 +11,7 @@
 // reference's scipy-RK45 backend (src/NeuralODE/nnModule.py:49-61) applied per walker instead of to the
 // whole flattened batch -- SURVEY.md finding 3: E_loc is insensitive to the step sequence (1e-10 relative).
 #pragma once
+#include <type_traits>
 #include "ff_common.h"
 #include "ff_plan.h"      // ff_geom_G and the shapes each kernel family is instantiated for
 
@@ -242,6 +243,44 @@ struct ff_stepper {
       else { habs *= fmax(0.2, 0.9 * ff_pow02(err, -0.2f)); rejected = 1; nrej++; }
     }
     if (!done && natt >= max_steps) { fail = 1; done = true; }
+    return acc;
+  }
+};
+
+// The stepper of the frame-writing flow kernels (CNF.generate(z, nframes): DESIGN.md 3u): one integration from ta to tb that lands
+// on every frame time t_k = ta + k (tb - ta) / (nf - 1) on its way.  A step that would pass the frame the walker is heading for is
+// shortened to end on it (as the last step of ff_stepper is clipped to tb), and the step size proposed before the shortening
+// stays the proposal for the step behind the frame: a frame does not reset the controller.  With nf = 2 the only frame ahead is tb
+// and every decision is ff_stepper's.
+struct ff_frame_stepper : ff_stepper {
+  double ta, tf, hkeep;   // start; time of frame kf; the proposal a shortened step replaced (0: the step was not shortened)
+  int kf, nf, landed;     // the frame the walker is heading for; frames in all; the frame the step just accepted ended on (-1: none)
+  FF_D double frame_time(int k) const { return k >= nf - 1 ? tb : ta + k * ((tb - ta) / (double)(nf - 1)); }
+  FF_D void begin(double ta_, double tb_, bool active, int nframes) {
+    ff_stepper::begin(ta_, tb_, active);
+    ta = ta_; nf = nframes; kf = 1; landed = -1; hkeep = 0.0;
+    tf = frame_time(1);
+  }
+  FF_D void plan() {
+    if (done) { h = 0.0; tnew = t; return; }
+    tnew = t + habs * dir;
+    hkeep = 0.0;
+    if (dir * (tnew - tf) > 0.0) {
+      tnew = tf;
+      if (kf < nf - 1) hkeep = habs;   // (the step onto the last frame is the clipped last step of every integration here)
+    }
+    h = tnew - t;
+    habs = fabs(h);
+  }
+  FF_D bool decide(double err, int max_steps) {
+    const bool acc = ff_stepper::decide(err, max_steps);
+    landed = -1;
+    if (acc && dir * (t - tf) >= 0.0) {
+      landed = kf;
+      if (hkeep > 0.0) habs = hkeep;
+      kf++;
+      tf = frame_time(kf);
+    }
     return acc;
   }
 };

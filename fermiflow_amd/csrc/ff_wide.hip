@@ -84,9 +84,12 @@ FF_D double ff_wide_sum(double* s_red, double* s_red2, int tid, double part) {
 // =====================================================================================================================
 // CNF.generate (MODE 0) / CNF.delta_logp (MODE 1): one wave per walker; lane l owns coordinates l and l + 64 and the
 // radii l, l + 64, ... (for MODE 1 also the share of Delta that its radii contribute: a plain quadrature).
-template <int D, int MODE, bool TAB>
+// MODE_ = FF_MODE_FRAMES: MODE 0 that writes the frames of the trajectory on its way (ff_frame_stepper)
+template <int D, int MODE_, bool TAB>
 __global__ void __launch_bounds__(FF_WAVE)
 ff_wide_flow_kernel(ff_fwd_args A, int n) {
+  constexpr bool FRAMES = MODE_ == FF_MODE_FRAMES;
+  constexpr int MODE = FRAMES ? 0 : MODE_;
   constexpr int NH = MODE == 0 ? 1 : 2;
   constexpr int NP = 1;                                  // coordinate slots per lane (M <= 64)
   constexpr int NQ = (FF_WIDE_RMAX + FF_WAVE - 1) / FF_WAVE;
@@ -128,8 +131,13 @@ ff_wide_flow_kernel(ff_fwd_args A, int n) {
 #pragma unroll
     for (int v = 0; v < NV; v++) { y[v] = 0.0; c0[v] = 0.0; c1[v] = 0.0; c2[v] = 0.0; c3[v] = 0.0; }
     if (own) y[0] = A.y_in[b * M + lane];
-    ff_stepper S;
-    S.begin(A.ta, A.tb, true);
+    std::conditional_t<FRAMES, ff_frame_stepper, ff_stepper> S;
+    if constexpr (FRAMES) {
+      S.begin(A.ta, A.tb, true, A.nframes);
+      if (own) A.y_out[b * M + lane] = y[0];   // frame 0
+    } else {
+      S.begin(A.ta, A.tb, true);
+    }
     ff_dp5_ctl C;
     C.rtol = A.rtol; C.atol = A.atol; C.nt_inv = 1.0 / (double)(M + (MODE == 1 ? 1 : 0)); C.max_steps = A.max_steps;
     C.hwarm = ff_open_step(ff_opt_load(A.h_init, true, A.h_scale < 0.0 ? 0 : b, A.y_in, 0.0) * fabs(A.h_scale), A.ta, A.tb, A.h_equal);
@@ -198,7 +206,18 @@ ff_wide_flow_kernel(ff_fwd_args A, int n) {
         out[0] = vi;
         if constexpr (MODE == 1) out[1] = -dsum;
       }
-      s = ff_dp5_consume<NV>(sv, S, C, y, c0, c1, c2, c3, out, wgt, gsum);
+#ifdef FF_HOSTSIM      // (compiled without contraction: nothing to pin)
+      constexpr int PIN_B = 0;
+#else
+      constexpr int PIN_B = FRAMES ? (TAB ? 1 : 2) : 0;      // the contraction of the mode-0 kernel with the same TAB (ff_dp5.h)
+#endif
+      s = ff_dp5_consume<NV, PIN_B>(sv, S, C, y, c0, c1, c2, c3, out, wgt, gsum);
+      if constexpr (FRAMES) {   // the step just accepted ended on a frame: the lane-to-address mapping of the final write below
+        if (sv == 6 && S.landed >= 0) {
+          if (own) A.y_out[((int64_t)S.landed * A.B + b) * M + lane] = y[0];
+          S.landed = -1;
+        }
+      }
       return s == 99;
     };
     if constexpr (STATIC_STAGES) {
@@ -224,7 +243,11 @@ ff_wide_flow_kernel(ff_fwd_args A, int n) {
     // -------------------------------------------------------------------- results
     const bool failed = S.fail != 0;
     const double bad = failed ? __builtin_nan("") : 0.0;
-    if (own) A.y_out[b * M + lane] = y[0] + bad;
+    if constexpr (FRAMES) {   // the frames the walker did not reach: NaN after a failure (an empty interval: the state itself)
+      for (int k = S.kf; k < A.nframes; k++) { if (own) A.y_out[((int64_t)k * A.B + b) * M + lane] = y[0] + bad; }
+    } else {
+      if (own) A.y_out[b * M + lane] = y[0] + bad;
+    }
     double delta = 0.0;
     if constexpr (MODE == 1) delta = gsum(y[NV - 1]);
     if (A.wcost) {
@@ -1047,6 +1070,7 @@ int ff_wide_dispatch_fwd(int mode, void* stream, int n, int d, const ff_fwd_args
   if (mode >= 2 && (a.fin.on & 2)) { ff_set_error("this build (FF_WIDE_NO_FIN) has no fused finish: ff_ode.compact_finish is not available"); return FF_EUNSUPPORTED; }
 #endif
   if (mode == 0) { if (d == 2) launch_wide_flow<2, 0>(stream, a, n, p); else launch_wide_flow<3, 0>(stream, a, n, p); }
+  else if (mode == FF_MODE_FRAMES) { if (d == 2) launch_wide_flow<2, FF_MODE_FRAMES>(stream, a, n, p); else launch_wide_flow<3, FF_MODE_FRAMES>(stream, a, n, p); }
   else if (mode == 1) { if (d == 2) launch_wide_flow<2, 1>(stream, a, n, p); else launch_wide_flow<3, 1>(stream, a, n, p); }
   else {
     const int T = p.param;

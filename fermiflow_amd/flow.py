@@ -1,6 +1,10 @@
 """Continuous normalizing flow wrapper (src/flow.py:6-55)."""
+import operator
+
 import torch
 
+from . import _lib as L
+from . import native
 from .NeuralODE.nnModule import solve_ivp_nnmodule
 
 
@@ -33,8 +37,21 @@ class CNF(torch.nn.Module):
         self.rtol, self.atol = 1e-6, 1e-8    # solve_ivp_nnmodule defaults, src/NeuralODE/nnModule.py:162
 
     def generate(self, z, nframes=None):
+        """x = z + int v dt over t_span.  With nframes = K: the trajectory at torch.linspace(*t_span, K) as a (K, *z.shape)
+        tensor without gradient (what the reference's odeint returns, src/flow.py:45-48), frames[0] = z -- one launch."""
         if nframes is not None:
-            raise NotImplementedError("generate(nframes=...) (animation frames) is outside the VMC hot path")
+            try:
+                if isinstance(nframes, bool):
+                    raise TypeError
+                k = operator.index(nframes)
+            except TypeError:
+                raise ValueError(f"generate: nframes must be an integer >= 1, got {nframes!r}") from None
+            if k < 1:
+                raise ValueError(f"generate: nframes must be an integer >= 1, got {nframes!r}")
+            z = L.dev(z.detach(), name="z")      # (a CPU tensor raises here: there is no fallback)
+            with torch.no_grad():
+                frames, _ = native.cnf_generate_frames(self.v_wrapper.v.net(), z, k, self.t_span[0], self.t_span[1], self.rtol, self.atol)
+            return frames
         return solve_ivp_nnmodule(self.v_wrapper, self.t_span, z, params_require_grad=False,
                                   rtol=self.rtol, atol=self.atol)
 

@@ -198,6 +198,20 @@ def cnf_generate(net, z, t0, t1, rtol, atol, want_stats=False, walker_cost=None,
     return (x, st) if want_stats else x
 
 
+def cnf_generate_frames(net, z, nframes, t0, t1, rtol, atol, walker_cost=None, walker_order=None, **warm):
+    """ff_cnf_generate_frames: (frames (nframes, B, n, d) at torch.linspace(t0, t1, nframes) with frames[0] = z, stats) --
+    one integration that lands on every frame time (csrc/ff_ode.h, ff_frame_stepper)."""
+    z = L.dev(z, name="z")
+    B, n, d = z.shape
+    nframes = int(nframes)
+    frames = torch.empty((max(nframes, 1), B, n, d), dtype=torch.float64, device=z.device)
+    st = _stats(z.device, True)
+    o = L.ode(t0, t1, rtol, atol, walker_cost=walker_cost, walker_order=walker_order, **warm)
+    L.check(L.lib().ff_cnf_generate_frames(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(z), nframes, L.ptr(frames), L.ptr(st)),
+            "ff_cnf_generate_frames")
+    return frames, st
+
+
 def cnf_delta_logp(net, x, t0, t1, rtol, atol, want_stats=False, walker_cost=None, walker_order=None, **warm):
     x = L.dev(x, name="x")
     B, n, d = x.shape

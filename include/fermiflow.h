@@ -269,6 +269,13 @@ int ff_radial_table_build(void* stream, const ff_net* net, double* table);
 /* CNF.generate (src/flow.py:42-44): x = z + int_{t0}^{t1} v dt. */
 int ff_cnf_generate(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode,
                     const double* z, double* x_out, int32_t* stats);
+/* CNF.generate(z, nframes) (src/flow.py:45-48): frames (nframes, B, n, d), frames[0] = z.
+ * ONE integration from t0 to t1 that lands on every frame time t_k = t0 + k (t1 - t0) / (nframes - 1): a step that would pass the
+ * next frame is shortened to end on it, and the step size proposed before the shortening stays the proposal behind the frame.
+ * The ff_ode fields mean what they mean for ff_cnf_generate (walker_h_out, walker_cost: of the whole interval), and so do stats.
+ * A walker whose integration fails has NaN in the frame it was heading for and in every later one.  nframes = 1 copies z. */
+int ff_cnf_generate_frames(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode,
+                           const double* z, int nframes, double* frames, int32_t* stats);
 /* CNF.delta_logp (src/flow.py:51-55): integrate (x,0) under (v,-div v) from t1 to t0 -> (z, delta). */
 int ff_cnf_delta_logp(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode,
                       const double* x, double* z_out, double* dlogp_out, int32_t* stats);
