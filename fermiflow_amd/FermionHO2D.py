@@ -15,6 +15,7 @@ import time
 import torch
 
 from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, Observables, checkpoint, frames, native
+from .sr import SR
 from .utils import make_adam
 
 
@@ -41,8 +42,20 @@ def build_parser():
                         help=".npz file for the radial densities and pair-distance distributions averaged over the run's iterations")
     parser.add_argument("--observe_rmax", type=float, default=6.0, help="largest radius / distance of the observables' histograms")
     parser.add_argument("--observe_bins", type=int, default=240, help="number of bins of the observables' histograms")
+    parser.add_argument("--optimizer", type=str, default="adam", choices=["adam", "sr"],
+                        help="adam: the reference's optimizer; sr: stochastic reconfiguration (fermiflow_amd/sr.py; not in the reference)")
+    parser.add_argument("--sr_lr", type=float, default=0.05, help="learning rate of --optimizer sr")
+    parser.add_argument("--sr_shift", type=float, default=1e-3, help="diagonal shift of the Fisher matrix of --optimizer sr")
     frames.add_arguments(parser)
     return parser
+
+
+def make_optimizer(args, model):
+    """the reference's Adam (default), or stochastic reconfiguration attached to the model's sweep"""
+    if args.optimizer == "sr":
+        model.sr = SR(model.parameters(), lr=args.sr_lr, shift=args.sr_shift)
+        return model.sr
+    return make_adam(model.parameters(), lr=1e-2)
 
 
 def main(argv=None):
@@ -73,7 +86,7 @@ def main(argv=None):
     cnf = CNF(v, (args.t0, args.t1))
     model = GSVMC(args.nup, args.ndown, orbitals, basedist, cnf, CoulombPairPotential(args.Z), sp_potential=HO())
     model.to(device=device)
-    optimizer = make_adam(model.parameters(), lr=1e-2)
+    optimizer = make_optimizer(args, model)
     if args.observe_out:
         model.observables = Observables(args.nup, args.ndown, dim=args.dim, rmax=args.observe_rmax, nbins=args.observe_bins, device=device)
     start_iter = 1

@@ -142,6 +142,8 @@ class _Sweep:
         self.profile = None
         # None, or an observables.Observables: every sweep then adds its physical walkers to it (one launch right after the flow pass)
         self.observables = None
+        # None, or an sr.SR (GSVMC only): every sweep then also leaves the Fisher matrix of the walkers' log-derivatives on it (_sweep)
+        self.sr = None
         self.fast_backward = True    # _SweepScalar: `gradE.backward()` hands the gradient views to .grad without running the graph
         # ODE step-size warm start inside the sweep; FERMIFLOW_WARM_START=0 restores the cold start
         self.warm_start = os.environ.get("FERMIFLOW_WARM_START", "1") != "0"
@@ -602,6 +604,14 @@ class GSVMC(_Sweep, torch.nn.Module):
                 prof.setdefault("adjoint_stats", []).append(adj[2])
             if prefetch:
                 self._prefetch(prefetch, go)
+            if getattr(self, "sr", None) is not None:
+                # stochastic reconfiguration (sr.py): per-walker log-derivatives by the direct kernel, their raw moments on the
+                # matrix cores, one all-reduce, the finish -- device tensors on model.sr, nothing waits for the host
+                sr = self.sr
+                sr.scores = native.cnf_adjoint_scores(net, r["z"], r["glogp0"], t0, t1, self.cnf.rtol, self.cnf.atol, **self._adjoint_open(he))
+                sums = native.sr_moments(sr.scores, Eloc, est)
+                D.all_reduce_sum_(sums)
+                sr.fisher, sr.obar, sr.grad = native.sr_finish(sums, sr.scores.shape[1])
             D.all_reduce_sum_(gp)
             self._mark(ev, "adjoint")
         if prof is not None:
@@ -654,6 +664,16 @@ class BetaVMC(_Sweep, torch.nn.Module):
         self._coll = Counter(dict(coll))
 
     _coll = None
+
+    # stochastic reconfiguration needs the categorical's Fisher block for the logits and the per-state baseline: not built
+    @property
+    def sr(self):
+        return None
+
+    @sr.setter
+    def sr(self, value):
+        if value is not None:
+            raise NotImplementedError("BetaVMC has no stochastic reconfiguration (the logits need the categorical's Fisher block): GSVMC only")
 
     # How the many-body states of a batch are drawn: "order_statistics" (default; below) or "reference" -- the reference's own draw,
     # Categorical(logits).sample((batch,)) on torch's CPU generator, sorted (src/VMC.py:90-96): after the same torch.manual_seed the state

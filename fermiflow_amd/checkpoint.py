@@ -22,7 +22,7 @@ import torch
 
 def save(path, model, optimizer, it, device=None, observables=None):
     ck = {"model": model.state_dict(), "optimizer": optimizer.state_dict(), "iter": int(it),
-          "rng_cpu": torch.get_rng_state()}
+          "rng_cpu": torch.get_rng_state(), "optimizer_kind": getattr(optimizer, "kind", "adam")}
     if observables is not None:
         ck["observables"] = observables.state_dict()
     if device is not None and torch.device(device).type == "cuda":
@@ -35,6 +35,9 @@ def save(path, model, optimizer, it, device=None, observables=None):
 def load(path, model, optimizer, device=None, observables=None):
     """Restores model / optimizer / RNG state in place; returns the iteration the checkpoint was written after."""
     ck = torch.load(path, map_location=device, weights_only=True)      # tensors, dicts, ints only: nothing to unpickle
+    kind = ck.get("optimizer_kind", "adam")      # (checkpoints without the key were written with Adam)
+    if kind != getattr(optimizer, "kind", "adam"):
+        raise ValueError(f"{path} was written with --optimizer {kind}")
     model.load_state_dict(ck["model"])
     optimizer.load_state_dict(ck["optimizer"])
     if "rng_cpu" in ck:

@@ -1,7 +1,11 @@
 // ff_adj_direct_body.inc -- body of the direct-evaluation adjoint kernel (ff_cnf_adj.hip), included twice: by ff_ode_adj_kernel
 // (LDS arrays declared statically) and by ff_ode_adj_lean_kernel (the same arrays as references into dynamic LDS).  Expects
 // N, D, MAXU, M, G, P, R, NV, CH and the arrays s_w, s_z, s_kb, s_err, s_ad, s_rad, s_rinv, s_ca, s_cb, s_ph, s_hd, s_pa, s_pb,
-// s_any, s_e2, s_st in scope.
+// s_any, s_e2, s_st in scope -- and SCORES (constexpr bool), J0, JN (constexpr int: the launch integrates the parameter gradient of
+// the lane's units j = J0 .. J0 + JN - 1 of its MAXU; 0 and MAXU everywhere but in the scores kernels).  SCORES = true is ff_ode_adj_scores_kernel: the same integration
+// with the per-walker seeds of ff_cnf_adjoint_scores (a_z = az_in[b], a_Delta = -1), the accepted steps' parameter integrands added
+// to row b of the (B, 3He+3Hm) scores -- per WALKER instead of per (workgroup, group-slot); A.rows points at the scores in this
+// variant; the per-workgroup rows and A.gx_out are not involved.  Every difference is under `if constexpr (SCORES)`: the SCORES = false instantiations compile to what they were.
   const int lane = threadIdx.x;
   const int g = lane / M, i = lane % M;
   const bool ingrp = g < G;
@@ -28,10 +32,11 @@
   // This lane's slice of the parameter-gradient row of (workgroup, group-slot): entries of its own units only,
   // so accepted steps are added with plain (non-atomic) read-modify-writes.  The lane zeroes its entries itself (this kernel runs
   // only when the tabulated kernel did not serve the call: a 12 MB memset in front of every call was the price of that otherwise).
-  double* const myrow = A.rows + ((int64_t)blockIdx.x * G + (ingrp ? g : 0)) * (3 * He + 3 * Hm);
+  double* const myrow = SCORES ? nullptr : A.rows + ((int64_t)blockIdx.x * G + (ingrp ? g : 0)) * (3 * He + 3 * Hm);
   constexpr int UC = M * MAXU;                 // hidden units per gradient chunk
   const int unit0 = A.unit0;
   const int nchunks = ((He > Hm ? He : Hm) + UC - 1) / UC;
+  if constexpr (!SCORES) {
   if (ingrp) {
     for (int t = 0; t < 2; t++) {
       const int H = t ? Hm : He;
@@ -41,6 +46,7 @@
           for (int c = 0; c < 3; c++) myrow[(t ? 3 * He : 0) + c * H + k] = 0.0;
       }
     }
+  }
   }
   auto row_add = [&](int t, int j, int c, double v) {
     const int k = unit0 + i + j * M, H = t ? Hm : He;
@@ -60,14 +66,33 @@
       const double wb = (ff_opt_load(A.w_e, valid, b, A.z_in, 0.0) - ff_opt_load(A.w_mean, valid && ws, wi, A.z_in, 0.0)) * A.w_scale;
       const double az0 = ff_opt_load(A.az_in, valid, b * M + i, A.z_in, 0.0), ad0 = ff_opt_load(A.ad_in, valid, b, A.z_in, 0.0);
       y[1] = ws ? wb * az0 : az0;
-      if (ingrp && i == 0) s_ad[g] = ws ? -wb : ad0;
+      if constexpr (SCORES) {
+        if (ingrp && i == 0) s_ad[g] = -1.0;
+      } else {
+        if (ingrp && i == 0) s_ad[g] = ws ? -wb : ad0;
+      }
+    }
+    // SCORES: row b of the output, the lane's entries: zeroed here, accepted steps added by plain read-modify-writes in the order
+    // row_add adds them to a workgroup row -- the row is the accumulator, as there (in registers the 6 MAXU sums of a lane put every
+    // instantiation that runs at 512 registers into scratch inside the step loop: DESIGN.md 3v)
+    double* const srow = SCORES ? A.rows + b * (int64_t)(3 * He + 3 * Hm) : nullptr;
+    auto score_entry = [&](int t, int j, int c) -> double* {
+      const int k = unit0 + i + (J0 + j) * M, H = t ? Hm : He;
+      return (valid && k < H) ? srow + (t ? 3 * He : 0) + c * H + k : nullptr;
+    };
+    bool rej_last = false;      // SCORES: this walker's own last decision was a rejection (statistics, below)
+    if constexpr (SCORES) {
+      for (int t = 0; t < 2; t++)
+        for (int j = 0; j < JN; j++)
+          for (int c = 0; c < 3; c++)
+            if (double* q = score_entry(t, j, c)) *q = 0.0;
     }
     // tent = B0*k0_theta + sum_{s=2..5} B_s*k_s_theta of the step under way (dropped if the step is rejected)
-    double tent[2][MAXU][3];
+    double tent[2][JN][3];
 #pragma unroll
     for (int t = 0; t < 2; t++)
 #pragma unroll
-      for (int j = 0; j < MAXU; j++)
+      for (int j = 0; j < JN; j++)
 #pragma unroll
         for (int c = 0; c < 3; c++) tent[t][j][c] = 0.0;
     ff_stepper S;
@@ -154,13 +179,19 @@
         s_cb[qg][p] = bb >= 0 ? 2.0 * ad * r : ad * r;
       }
       __syncthreads();
-      nev++;
+      if constexpr (SCORES) {
+        // the evaluations THIS walker would take alone (its group mates' probe and their passes through stage 0 are not its own):
+        // stats[0] is then the sum over one-walker calls, whatever the grouping
+        nev += (s == -2 || (s == -1 ? (!S.done && !warm) : (s == 0 ? rej_last : !S.done))) ? 1 : 0;
+      } else {
+        nev++;
+      }
       // ------------------------------------------------------------------ unit phase
-      double cur[2][MAXU][3];
+      double cur[2][JN][3];
 #pragma unroll
       for (int t = 0; t < 2; t++)
 #pragma unroll
-        for (int j = 0; j < MAXU; j++) cur[t][j][0] = cur[t][j][1] = cur[t][j][2] = 0.0;
+        for (int j = 0; j < JN; j++) cur[t][j][0] = cur[t][j][1] = cur[t][j][2] = 0.0;
 #pragma unroll
       for (int t = 0; t < 2; t++) {
         const int H = t ? Hm : He;
@@ -192,11 +223,11 @@
               h0 = fma(w2, sg, h0);
               h1 = fma(w2w1, s1, h1);
               h2 = fma(w2w1 * w[j].w1, s2, h2);
-              if (mine) {
+              if (mine && j >= J0 && j < J0 + JN) {      // (J0 = 0, JN = MAXU except in the scores kernels: all of the lane's units)
                 const double w1rs2 = w[j].w1 * r * s2;
-                cur[t][j][0] += w2 * fma(ca * r, s1, cb * (s1 + w1rs2));
-                cur[t][j][1] += fma(ca * w2, s1, cb * w2w1 * s2);
-                cur[t][j][2] += mk[j] * fma(ca, sg, cb * w[j].w1 * s1);
+                cur[t][j - J0][0] += w2 * fma(ca * r, s1, cb * (s1 + w1rs2));
+                cur[t][j - J0][1] += fma(ca * w2, s1, cb * w2w1 * s2);
+                cur[t][j - J0][2] += mk[j] * fma(ca, sg, cb * w[j].w1 * s1);
               }
             }
           }
@@ -258,7 +289,7 @@
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
-          for (int j = 0; j < MAXU; j++)
+          for (int j = 0; j < JN; j++)
 #pragma unroll
             for (int c = 0; c < 3; c++) tent[t][j][c] = FF_B0 * cur[t][j][c];
         double p0 = 0.0, p1 = 0.0;
@@ -296,7 +327,7 @@
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
-          for (int j = 0; j < MAXU; j++)
+          for (int j = 0; j < JN; j++)
 #pragma unroll
             for (int c = 0; c < 3; c++) tent[t][j][c] = FF_B0 * cur[t][j][c];
         s = 1;
@@ -305,7 +336,7 @@
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
-          for (int j = 0; j < MAXU; j++)
+          for (int j = 0; j < JN; j++)
 #pragma unroll
             for (int c = 0; c < 3; c++) tent[t][j][c] = fma(bw, cur[t][j][c], tent[t][j][c]);
         if (s == 1) {
@@ -344,12 +375,19 @@
 #pragma unroll
         for (int t = 0; t < 2; t++)
 #pragma unroll
-          for (int j = 0; j < MAXU; j++)
+          for (int j = 0; j < JN; j++)
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-              if (acc) row_add(t, j, c, h * tent[t][j][c]);
+              if constexpr (SCORES) {
+                if (acc) {
+                  if (double* q = score_entry(t, j, c)) *q += h * tent[t][j][c];
+                }
+              } else {
+                if (acc) row_add(t, j, c, h * tent[t][j][c]);
+              }
               tent[t][j][c] = acc ? FF_B0 * cur[t][j][c] : 0.0;   // FSAL: k6_theta opens the next step
             }
+        if constexpr (SCORES) rej_last = was_active && !acc;
         S.plan();
         const int any = ff_wave_or(&s_any, lane, S.done ? 0 : ((was_active && !acc) ? 3 : 1));
         if (!any) break;
@@ -359,12 +397,23 @@
     if (valid) {
       // failed integration (NaN error norm, max_steps): NaN into this walker's x-gradient and into the parameter gradient
       const double bad = S.fail ? __builtin_nan("") : 0.0;
-      if (A.gx_out) A.gx_out[b * M + i] = y[1] + bad;
+      if constexpr (SCORES) {
+        if (S.fail) {      // every entry of the row
+          for (int t = 0; t < 2; t++)
+            for (int j = 0; j < JN; j++)
+              for (int c = 0; c < 3; c++)
+                if (double* q = score_entry(t, j, c)) *q = bad;
+        }
+      } else {
+        if (A.gx_out) A.gx_out[b * M + i] = y[1] + bad;
+      }
       if (i == 0) {
-        if (S.fail && unit0 == 0) row_add(0, 0, 0, bad);
+        if constexpr (!SCORES) {
+          if (S.fail && unit0 == 0) row_add(0, 0, 0, bad);
+        }
         if (A.h_out) A.h_out[b] = hmax_acc > 0.0 ? hmax_acc : hwarm;
         if (A.wcost) A.wcost[b] = S.nacc + S.nrej;
-        if (A.stats && unit0 == 0) { atomicAdd(&s_st[0], nev); atomicMax(&s_st[1], S.nacc); atomicAdd(&s_st[2], S.nrej); if (S.fail) atomicMax(&s_st[3], 1); }
+        if (A.stats && unit0 == 0 && J0 == 0) { atomicAdd(&s_st[0], nev); atomicMax(&s_st[1], S.nacc); atomicAdd(&s_st[2], S.nrej); if (S.fail) atomicMax(&s_st[3], 1); }
       }
     }
     __syncthreads();

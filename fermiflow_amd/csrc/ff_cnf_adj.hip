@@ -39,7 +39,8 @@ struct ff_adj_args {
   const int32_t* w_index;   // optional (B): which entry of w_mean is walker b's baseline (BetaVMC: its many-body state); NULL: entry 0
   double w_scale;
   double* gx_out;       // (B, M)  gradient wrt x = z(t1); may be NULL
-  double* rows;         // (gridDim.x * G, 3He+3Hm) per-(workgroup, group-slot) parameter-gradient partials (direct kernel)
+  double* rows;         // (gridDim.x * G, 3He+3Hm) per-(workgroup, group-slot) parameter-gradient partials (direct kernel);
+                        // ff_ode_adj_scores_kernel: the (B, 3He+3Hm) per-walker rows it writes
   double* trows;        // (gridDim.x, 2, FF_DEP_NLDS, FF_DEP_ROW) private coefficient tables, then Wtot (tabulated kernel)
   double* off_table;    // one double, zeroed per call: set to 1 when a radius falls off the deposit table
   int32_t* stats;
@@ -75,6 +76,33 @@ ff_ode_adj_kernel(ff_adj_args A) {
   __shared__ double s_e2[64];
 
   __shared__ int s_st[4];   // ODE statistics of this workgroup's walkers (LDS: nothing loop-carried in registers)
+  constexpr bool SCORES = false;
+  constexpr int J0 = 0, JN = MAXU;
+#include "ff_adj_direct_body.inc"
+}
+
+// Per-walker log-derivatives (ff_cnf_adjoint_scores): the same body with SCORES = true.  Always direct evaluation -- no early
+// return for a usable radial table, no deposit table --, A.rows is the (B, 3He+3Hm) output, A.az_in the seeds glogp0, a_Delta = -1.
+// A launch keeps the parameter integrands of at most FF_SCORES_JN(MAXU) of a lane's MAXU units (j = J0 .. J0 + JN - 1) in registers: with
+// all of them the instantiations at MAXU >= 6 spill inside the step loop, as their ff_ode_adj_kernel twins at MAXU >= 7 do.  Every
+// launch evaluates all units in the twin's order -- the heads, hence the trajectories, are the twin's bit for bit.
+#define FF_SCORES_JN(MAXU) ((MAXU) > 13 ? 3 : 5)      // (the side-by-side sigmoids of 16 units leave room for three)
+template <int N, int D, int MAXU, int J0, int JN>
+__global__ void __launch_bounds__(FF_WAVE)
+ff_ode_adj_scores_kernel(ff_adj_args A) {
+  using Gm = ff_geom<N, D>;
+  constexpr int M = Gm::M, G = Gm::G, P = Gm::P, R = Gm::RA;
+  constexpr int NV = 2;
+  __shared__ ff_wtab s_w[2][FF_HPAD];
+  __shared__ double s_z[G][M], s_kb[G][M], s_err[G][M], s_ad[G];
+  __shared__ double s_rad[G][R], s_rinv[G][R], s_ca[G][R], s_cb[G][R];
+  constexpr int CH = 8;
+  __shared__ double s_ph[G][M][CH][3], s_hd[G][R][3];
+  __shared__ int s_pa[R], s_pb[R], s_any;
+  __shared__ double s_e2[64];
+  __shared__ int s_st[4];
+  constexpr bool SCORES = true;
+  static_assert(J0 >= 0 && JN >= 1 && J0 + JN <= MAXU, "unit block outside the lane's units");
 #include "ff_adj_direct_body.inc"
 }
 
@@ -112,6 +140,8 @@ ff_ode_adj_lean_kernel(ff_adj_args A) {
   constexpr int CH = ff_adj_smem<N, D>::CH;
   auto& s_ph = sm.s_ph; auto& s_hd = sm.s_hd; auto& s_pa = sm.s_pa; auto& s_pb = sm.s_pb; auto& s_any = sm.s_any;
   auto& s_e2 = sm.s_e2; auto& s_st = sm.s_st;
+  constexpr bool SCORES = false;
+  constexpr int J0 = 0, JN = MAXU;
 #include "ff_adj_direct_body.inc"
 }
 
@@ -794,6 +824,32 @@ static void launch_adj(void* stream, const ff_adj_args& a_in, const ff_plan& p) 
   }
 }
 
+// ff_cnf_adjoint_scores: the SCORES instantiations of the direct body, one launch per chunk of M*MAXU hidden units as above and,
+// within a chunk, per block of FF_SCORES_JN(MAXU) units of a lane
+template <int N, int D, int MAXU, int J0>
+static void launch_scores_blocks(void* stream, const ff_adj_args& a, const ff_plan& p) {
+  constexpr int JN = MAXU - J0 < FF_SCORES_JN(MAXU) ? MAXU - J0 : FF_SCORES_JN(MAXU);
+  FF_LAUNCH((ff_ode_adj_scores_kernel<N, D, MAXU, J0, JN>), adj_grid(a.B, p), FF_WAVE, stream, a);
+  if constexpr (J0 + JN < MAXU) launch_scores_blocks<N, D, MAXU, J0 + JN>(stream, a, p);
+}
+
+template <int N, int D>
+static void launch_scores(void* stream, const ff_adj_args& a_in, const ff_plan& p) {
+  constexpr int M = ff_geom<N, D>::M;
+  constexpr int MU_64 = (64 + M - 1) / M > 16 ? 16 : (64 + M - 1) / M, MU_50 = (50 + M - 1) / M > 16 ? 16 : (50 + M - 1) / M;
+  const int hmax = a_in.net.He > a_in.net.Hm ? a_in.net.He : a_in.net.Hm;
+  ff_adj_args a = a_in;
+  if (MU_50 < MU_64 && hmax <= MU_50 * M) {
+    a.unit0 = 0;
+    launch_scores_blocks<N, D, MU_50, 0>(stream, a, p);
+  } else {
+    for (int u0 = 0; u0 < hmax; u0 += MU_64 * M) {
+      a.unit0 = u0;
+      launch_scores_blocks<N, D, MU_64, 0>(stream, a, p);
+    }
+  }
+}
+
 // ff_ode.walker_h_equal for the one-walker-per-workgroup adjoint kernels: their opening steps are rounded HERE, in a launch of its own
 // (5 us in front of 1-30 ms), not in their walker prologue as everywhere else.  With ff_open_step in that prologue -- and the flag zero --
 // ff_wide_adjtab_kernel<3, 4, 1> failed every walker of a 20-particle batch on the GPU (not in the host simulator; no scratch, four
@@ -853,6 +909,41 @@ int ff_cnf_adjoint_energy(void* stream, int64_t B, int n, int d, const ff_net* n
   FF_CHECK(B == 0 || (eloc && e_mean), FF_EINVAL, "ff_cnf_adjoint_energy: null pointer");
   return adjoint_impl(stream, B, n, d, net, ode, z_t0, glogp0, nullptr, eloc, e_mean, mean_index, scale, grad_x, grad_params, workspace,
                       stats);
+}
+
+// --- per-walker log-derivatives O_b = d[logp0(z(x_b)) - Delta(x_b)]/dtheta at fixed x_b: row b is the parameter gradient of
+// ff_cnf_adjoint for walker b alone with the seeds a_z = glogp0[b], a_Delta = -1.  The narrow family only (group and grid of the
+// direct adjoint at the shape).  The kernels accumulate in the output rows themselves: no workspace (the query returns 0; it and the
+// argument are part of the signature for the one-walker-per-workgroup twin, which will need one).
+static int scores_plan(int n, int d, ff_plan& dir) {
+  if (ff_wide_forced()) return ff_refuse(FF_EUNSUPPORTED, "ff_scores", "the one-walker-per-workgroup family (FF_WIDE / ff_set_kernel_family) has no scores kernel");
+  dir = adj_plan(n, d, false).dir;
+  if (dir.family != FF_FAMILY_DIRECT) return ff_refuse(FF_EUNSUPPORTED, "ff_scores", "served for n <= 12 in d = 2 and n = 2, 3, 4 in d = 3");
+  return FF_OK;
+}
+
+size_t ff_cnf_adjoint_scores_workspace_bytes(int64_t B, int n, int d, int He, int Hm) {
+  (void)B; (void)n; (void)d; (void)He; (void)Hm;
+  return 0;
+}
+
+int ff_cnf_adjoint_scores(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* z_t0,
+                          const double* glogp0, double* scores, void* workspace, int32_t* stats) {
+  (void)workspace;
+  if (const int st = ff_check_flow("ff_scores", B >= 0 && n > 0 && d > 0 && scores, net, ode)) return st;
+  ff_plan dir = FF_NO_PLAN;
+  if (const int st = scores_plan(n, d, dir)) return st;      // (refused before anything is launched)
+  if (B == 0) return FF_OK;
+  FF_CHECK(z_t0 && glogp0, FF_EINVAL, "ff_scores: null pointer");
+  ff_adj_args a = {};
+  ff_fill_common(a, B, net, ode, true);
+  a.net.radial_table = nullptr;      // (direct evaluation: the kernel reads no table)
+  a.z_in = z_t0; a.az_in = glogp0; a.rows = scores; a.stats = stats;
+#define FF_ND(N_, D_, S_) if (n == N_ && d == D_) launch_scores<N_, D_>(stream, a, dir);
+  FF_NARROW_SHAPES(FF_ND)
+#undef FF_ND
+  FF_LAUNCH_CHECK();
+  return FF_OK;
 }
 
 static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode, const double* z_t0,
@@ -932,3 +1023,5 @@ static int adjoint_impl(void* stream, int64_t B, int n, int d, const ff_net* net
 }
 
 }  // extern "C"
+
+#include "ff_sr.h"   // moments of the per-walker scores on the fp64 matrix cores (ff_sr_moments, ff_sr_finish)

@@ -252,6 +252,49 @@ def cnf_adjoint(net, y_start, a_z, a_d, t_from, t_to, rtol, atol, need_gx=True, 
     return (gx, gp, st) if want_stats else (gx, gp)
 
 
+def cnf_adjoint_scores(net, z_t0, glogp0, t_from, t_to, rtol, atol, want_stats=False, walker_order=None, **warm):
+    """ff_cnf_adjoint_scores: the per-walker log-derivatives (B, 3He+3Hm) of walkers whose flow ends in z_t0 with
+    glogp0 = grad_z logp0(z_t0) (both as native.eloc returns them).  NotImplementedError outside the narrow adjoint's shapes."""
+    z = L.dev(z_t0, name="z_t0"); g0 = L.dev(glogp0, name="glogp0")
+    B, n, d = z.shape
+    scores = torch.empty((B, net.nparams), dtype=torch.float64, device=z.device)
+    st = _stats(z.device, want_stats)
+    o = L.ode(t_from, t_to, rtol, atol, walker_order=walker_order, **warm)
+    L.check(L.lib().ff_cnf_adjoint_scores(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(z), L.ptr(g0), L.ptr(scores), None,      # (no workspace: include/fermiflow.h)
+                                          L.ptr(st)), "ff_cnf_adjoint_scores")
+    return (scores, st) if want_stats else scores
+
+
+_SR_WS = {}      # (device, stream, B, P) -> workspace of ff_sr_moments (partial tiles; written in full by every call)
+
+
+def sr_moments(scores, eloc, e_mean):
+    """ff_sr_moments: the raw sums [S_raw (P*P) | o_sum (P) | g_sum (P) | sum(e - E) | B] of scores (B, P) -- all-reduce them,
+    then sr_finish.  e_mean: device tensor whose first element is E."""
+    scores = L.dev(scores, name="scores"); e = L.dev(eloc, name="eloc"); em = L.dev(e_mean.reshape(-1)[:1], name="e_mean")
+    B, P = scores.shape
+    nbytes = L.lib().ff_sr_moments_workspace_bytes(L.i64(B), int(P))
+    key = (str(scores.device), int(torch.cuda.current_stream(scores.device).cuda_stream), int(B), int(P))
+    ws = _SR_WS.get(key)
+    if ws is None:
+        if len(_SR_WS) > 16:
+            _SR_WS.clear()
+        ws = _SR_WS[key] = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=scores.device)
+    sums = torch.empty(P * P + 2 * P + 2, dtype=torch.float64, device=scores.device)
+    L.check(L.lib().ff_sr_moments(L.stream(), L.i64(B), int(P), L.ptr(scores), L.ptr(e), L.ptr(em), L.ptr(sums), L.ptr(ws)), "ff_sr_moments")
+    return sums
+
+
+def sr_finish(sums, P):
+    """ff_sr_finish: (fisher (P, P), obar (P), grad (P)) from the (all-reduced) sums of sr_moments."""
+    sums = L.dev(sums, name="sums")
+    P = int(P)
+    f = dict(dtype=torch.float64, device=sums.device)
+    fisher, obar, grad = torch.empty((P, P), **f), torch.empty(P, **f), torch.empty(P, **f)
+    L.check(L.lib().ff_sr_finish(L.stream(), P, L.ptr(sums), L.ptr(fisher), L.ptr(obar), L.ptr(grad)), "ff_sr_finish")
+    return fisher, obar, grad
+
+
 COMPACT_WORKSPACE_BYTES = 32 << 30     # eloc(compact=None): beyond this many bytes of full workspace, ask for the compact one
 
 

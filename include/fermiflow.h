@@ -297,6 +297,32 @@ int ff_cnf_adjoint_energy(void* stream, int64_t B, int n, int d, const ff_net* n
                           const double* z_t0, const double* glogp0, const double* eloc, const double* e_mean,
                           const int32_t* mean_index, double scale,
                           double* grad_x, double* grad_params, void* workspace, int32_t* stats);
+/* Per-walker log-derivatives ("scores") O_b = d[logp0(z(x_b)) - Delta(x_b)]/dtheta at fixed x_b, the input of stochastic
+ * reconfiguration: row b of scores (B, 3*He + 3*Hm; Backflow.parameters() order) is the grad_params of ff_cnf_adjoint for
+ * walker b ALONE with the seeds a_z = glogp0[b], a_d = -1 (ff_cnf_adjoint_energy with w_b = 1).  Always by direct evaluation
+ * (net->radial_table is ignored); the same accepted steps, added in the same order, as the direct kernel of ff_cnf_adjoint.
+ * A failed integration (non-finite error norm, max_steps) puts NaN into EVERY entry of that walker's row.  stats as for
+ * ff_cnf_adjoint, with stats[0] counting the evaluations each walker would take alone: the sum over one-walker calls.
+ * Shapes: those of the several-walkers-per-wave adjoint (d = 2: n <= 12; d = 3: n = 2, 3, 4); any other shape, and the
+ * one-walker-per-workgroup family forced (FF_WIDE=1 / ff_set_kernel_family(1)), is refused before anything is launched with
+ * FF_EUNSUPPORTED and ff_last_error() = "ff_scores: ...".  B = 0 is a no-op.  The kernels accumulate in the rows of `scores`
+ * themselves: the workspace query returns 0 and workspace may be NULL (both belong to the signature for the kernels of the
+ * other family, which will need one). */
+size_t ff_cnf_adjoint_scores_workspace_bytes(int64_t B, int n, int d, int He, int Hm);
+int ff_cnf_adjoint_scores(void* stream, int64_t B, int n, int d, const ff_net* net, const ff_ode* ode,
+                          const double* z_t0, const double* glogp0, double* scores, void* workspace, int32_t* stats);
+/* Moments of the scores (B, P), 1 <= P <= 1536, on the fp64 matrix cores, as RAW sums -- ranks add them with one all-reduce:
+ *   sums = [ S_raw = sum_b O_b O_b^T  (P*P) | o_sum = sum_b O_b (P) | g_sum = sum_b O_b (eloc[b] - e_mean[0]) (P) |
+ *            sum_b (eloc[b] - e_mean[0]) | B ]                      (e_mean: DEVICE array)
+ * Deterministic: walkers are summed in chunks of 2048 in walker order, the chunks in chunk order, without floating-point
+ * atomics -- bit-identical from run to run; S_raw is exactly symmetric.  A NaN row makes the sums it enters NaN.  B = 0 gives
+ * zeros.  ff_sr_finish turns the (all-reduced) sums into
+ *   fisher = S_raw / B - obar obar^T (P,P; exactly symmetric)   obar = o_sum / B   grad = g_sum / B - obar * sum(e - E) / B
+ * (a count of zero gives NaN).  Refusals carry "ff_sr: ..."; the workspace query returns 0 outside the limits. */
+size_t ff_sr_moments_workspace_bytes(int64_t B, int P);
+int ff_sr_moments(void* stream, int64_t B, int P, const double* scores, const double* eloc, const double* e_mean,
+                  double* sums, void* workspace);
+int ff_sr_finish(void* stream, int P, const double* sums, double* fisher, double* obar, double* grad);
 
 /* ---- local energy (src/VMC.py:46-55 via src/utils.py:40-65) --------------------------------- */
 /* Two launches: (1) a fused per-walker Dormand-Prince pass integrating z, J = dz/dx, the x-Laplacian of z,
