@@ -11,6 +11,7 @@ import time
 import torch
 
 from . import HO2D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, BetaVMC, Observables, checkpoint, frames
+from .sr import BetaSR
 from .utils import make_adam
 
 
@@ -37,8 +38,22 @@ def build_parser():
                         help=".npz file for the radial densities and pair-distance distributions averaged over the run's iterations")
     parser.add_argument("--observe_rmax", type=float, default=6.0, help="largest radius / distance of the observables' histograms")
     parser.add_argument("--observe_bins", type=int, default=240, help="number of bins of the observables' histograms")
+    parser.add_argument("--optimizer", type=str, default="adam", choices=["adam", "sr"],
+                        help="adam: the reference's optimizer; sr: stochastic reconfiguration (fermiflow_amd/sr.py, BetaSR; not in the reference)")
+    parser.add_argument("--sr_lr", type=float, default=0.05, help="learning rate of --optimizer sr (flow parameters)")
+    parser.add_argument("--sr_shift", type=float, default=1e-3, help="diagonal shift of the flow parameters' Fisher matrix of --optimizer sr")
+    parser.add_argument("--sr_lr_phi", type=float, default=None, help="learning rate of the state logits of --optimizer sr (default: --sr_lr)")
+    parser.add_argument("--sr_shift_phi", type=float, default=None, help="diagonal shift of the logits' Fisher matrix of --optimizer sr (default: --sr_shift)")
     frames.add_arguments(parser)
     return parser
+
+
+def make_optimizer(args, model):
+    """the reference's Adam (default), or stochastic reconfiguration attached to the model's sweep"""
+    if args.optimizer == "sr":
+        model.sr = BetaSR(model, lr=args.sr_lr, shift=args.sr_shift, lr_phi=args.sr_lr_phi, shift_phi=args.sr_shift_phi)
+        return model.sr
+    return make_adam(model.parameters(), lr=1e-2)
 
 
 def main(argv=None):
@@ -65,7 +80,7 @@ def main(argv=None):
     model = BetaVMC(args.beta, args.nup, args.ndown, args.deltaE, args.boltzmann, HO2D(), FreeFermion(device=device), cnf,
                     CoulombPairPotential(args.Z), sp_potential=HO())
     model.to(device=device)
-    optimizer = make_adam(model.parameters(), lr=1e-2)
+    optimizer = make_optimizer(args, model)
     if args.observe_out:
         model.observables = Observables(args.nup, args.ndown, dim=2, rmax=args.observe_rmax, nbins=args.observe_bins, device=device)
     start_iter = 1

@@ -665,15 +665,19 @@ class BetaVMC(_Sweep, torch.nn.Module):
 
     _coll = None
 
-    # stochastic reconfiguration needs the categorical's Fisher block for the logits and the per-state baseline: not built
+    # stochastic reconfiguration of the joint p(n, x) = mu_n p_n(x): sr.BetaSR (per-state Fisher block of the flow, the categorical's
+    # exact block for the logits); a plain SR knows neither the per-state baseline nor the logits' block and is refused
     @property
     def sr(self):
-        return None
+        return self.__dict__.get("_sr")
 
     @sr.setter
     def sr(self, value):
-        if value is not None:
-            raise NotImplementedError("BetaVMC has no stochastic reconfiguration (the logits need the categorical's Fisher block): GSVMC only")
+        from .sr import BetaSR
+        if value is not None and not isinstance(value, BetaSR):
+            raise NotImplementedError("BetaVMC takes stochastic reconfiguration as a BetaSR (fermiflow_amd/sr.py: per-state Fisher block "
+                                      "and the categorical's block for the logits), not " + type(value).__name__)
+        self.__dict__["_sr"] = value
 
     # How the many-body states of a batch are drawn: "order_statistics" (default; below) or "reference" -- the reference's own draw,
     # Categorical(logits).sample((batch,)) on torch's CPU generator, sorted (src/VMC.py:90-96): after the same torch.manual_seed the state
@@ -821,6 +825,17 @@ class BetaVMC(_Sweep, torch.nn.Module):
             self._mark(ev, "estimator")
             _, gp = native.cnf_adjoint(net, r["z"], r["glogp0"], None, t0, t1, self.cnf.rtol, self.cnf.atol, need_gx=False,
                                        energy=(Eloc, mean_e, 1.0 / nglob, ws), **self._adjoint_open(he))
+            sr = self.sr
+            if sr is not None:
+                # stochastic reconfiguration (sr.BetaSR): per-walker log-derivatives by the direct kernel, their raw per-state moments
+                # (matrix cores; the baseline by state), one all-reduce, the finish; the logits' block is exact -- device tensors on
+                # model.sr, nothing waits for the host
+                sr.scores = native.cnf_adjoint_scores(net, r["z"], r["glogp0"], t0, t1, self.cnf.rtol, self.cnf.atol, **self._adjoint_open(he))
+                sums = native.sr_state_moments(sr.scores, Eloc, ws, mean_e, Ns)
+                D.all_reduce_sum_(sums)
+                sr.fisher, sr.obar_state, sr.grad = native.sr_state_finish(sums, sr.scores.shape[1], Ns)
+                mu_states = torch.exp(logp_all)
+                sr.fisher_phi = torch.diag(mu_states) - torch.outer(mu_states, mu_states)
             D.all_reduce_sum_(gp)
             self._mark(ev, "adjoint")
         if prof is not None:

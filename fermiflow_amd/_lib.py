@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FERMIFLOW_LIB") or os.path.join(_HERE, "libfermiflow_hip.so")   # env: A/B builds in tools/
 _LIB = None
 
-ABI_VERSION = 109      # ff_version() of the library this binding was written against (include/fermiflow.h)
+ABI_VERSION = 110      # ff_version() of the library this binding was written against (include/fermiflow.h)
 
 SYMBOLS = [
     "ff_version", "ff_last_error", "ff_fermion_states", "ff_slater_logabsdet_fwd", "ff_slater_logabsdet_bwd", "ff_logprob",
@@ -21,6 +21,7 @@ SYMBOLS = [
     "ff_eloc_workspace_bytes", "ff_eloc", "ff_eloc_sensitivities", "ff_eloc_finish", "ff_reduce_moments", "ff_state_sums", "ff_beta_buffer_doubles", "ff_beta_state_partials", "ff_beta_finish", "ff_logprob3d", "ff_mcmc_sample_noise3d", "ff_mcmc_sample3d", "ff_eloc_finish3d", "ff_backflow_v_div_f32", "ff_walker_order_workspace_bytes", "ff_walker_order", "ff_set_kernel_family", "ff_set_sens_precision", "ff_shutdown", "ff_walker_order_mean", "ff_energy_estimate_workspace_bytes", "ff_energy_estimate", "ff_mlp_eval_nd", "ff_backflow_vjp", "ff_eloc_nd", "ff_eloc_nd_workspace_bytes", "ff_rng_fill3d", "ff_walker_schedule", "ff_scale_counts", "ff_comm_unique_id", "ff_comm_init", "ff_comm_allreduce", "ff_comm_destroy", "ff_adam_step",
     "ff_observe_buffer_bytes", "ff_observe_accumulate", "ff_kernel_plan",
     "ff_cnf_adjoint_scores_workspace_bytes", "ff_cnf_adjoint_scores", "ff_sr_moments_workspace_bytes", "ff_sr_moments", "ff_sr_finish",
+    "ff_sr_state_moments_workspace_bytes", "ff_sr_state_moments", "ff_sr_state_finish",
 ]
 
 
@@ -66,7 +67,7 @@ def lib():
         _LIB.ff_beta_buffer_doubles.restype = C.c_size_t
         _LIB.ff_energy_estimate_workspace_bytes.restype = C.c_size_t
         _LIB.ff_observe_buffer_bytes.restype = C.c_size_t
-        for name in ("ff_cnf_adjoint_scores_workspace_bytes", "ff_sr_moments_workspace_bytes"):
+        for name in ("ff_cnf_adjoint_scores_workspace_bytes", "ff_sr_moments_workspace_bytes", "ff_sr_state_moments_workspace_bytes"):
             if hasattr(_LIB, name):      # (FERMIFLOW_LIB may name an A/B build of an earlier commit with the same ABI version: tools/probes/sr_rate.py)
                 getattr(_LIB, name).restype = C.c_size_t
     return _LIB

@@ -295,6 +295,43 @@ def sr_finish(sums, P):
     return fisher, obar, grad
 
 
+def sr_state_moments(scores, eloc, walker_state, mean_e, nstates):
+    """ff_sr_state_moments: the raw sums [S_raw (P*P) | o_state (nstates*P) | g_sum (P) | c_state (nstates)] of scores (B, P) whose
+    walkers are in the many-body states walker_state (int32, SORTED ascending); g_sum = sum_b O_b (eloc[b] - mean_e[state_b]) --
+    all-reduce them, then sr_state_finish."""
+    scores = L.dev(scores, name="scores"); e = L.dev(eloc, name="eloc"); me = L.dev(mean_e, name="mean_e")
+    st = L.dev(walker_state, torch.int32, "walker_state")
+    B, P = scores.shape
+    ns = int(nstates)
+    ws = _sr_state_ws(scores.device, B, P, ns)
+    sums = torch.empty(P * P + ns * P + P + ns, dtype=torch.float64, device=scores.device)
+    L.check(L.lib().ff_sr_state_moments(L.stream(), L.i64(B), int(P), ns, L.ptr(scores), L.ptr(e), L.ptr(st), L.ptr(me), L.ptr(sums), L.ptr(ws)),
+            "ff_sr_state_moments")
+    return sums
+
+
+def _sr_state_ws(device, B, P, nstates):
+    nbytes = L.lib().ff_sr_state_moments_workspace_bytes(L.i64(B), int(P), int(nstates))
+    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream), int(B), int(P), int(nstates))
+    ws = _SR_WS.get(key)
+    if ws is None:
+        if len(_SR_WS) > 16:
+            _SR_WS.clear()
+        ws = _SR_WS[key] = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=device)
+    return ws
+
+
+def sr_state_finish(sums, P, nstates):
+    """ff_sr_state_finish: (fisher (P, P), obar_state (nstates, P), grad (P)) from the (all-reduced) sums of sr_state_moments."""
+    sums = L.dev(sums, name="sums")
+    P, ns = int(P), int(nstates)
+    f = dict(dtype=torch.float64, device=sums.device)
+    fisher, obar, grad = torch.empty((P, P), **f), torch.empty((ns, P), **f), torch.empty(P, **f)
+    ws = _sr_state_ws(sums.device, 0, P, ns)      # (the finish needs no more than the query gives for an empty batch)
+    L.check(L.lib().ff_sr_state_finish(L.stream(), P, ns, L.ptr(sums), L.ptr(fisher), L.ptr(obar), L.ptr(grad), L.ptr(ws)), "ff_sr_state_finish")
+    return fisher, obar, grad
+
+
 COMPACT_WORKSPACE_BYTES = 32 << 30     # eloc(compact=None): beyond this many bytes of full workspace, ask for the compact one
 
 

@@ -111,7 +111,7 @@ typedef struct ff_ode {
   int32_t walker_h_equal;
 } ff_ode;
 
-int ff_version(void);   /* 109; changes whenever a struct of this header changes layout (the Python binding checks it) */
+int ff_version(void);   /* 110; changes whenever a struct of this header changes layout (the Python binding checks it) */
 /* Releases what the library created lazily: the side stream and the two events per device of the routed local-energy pass
  * (created on the first such call on a device, shared by all host threads under a mutex).  Call when no call of this library is
  * in flight; the next routed call creates them again.  Everything else the library touches is caller-owned memory. */
@@ -323,6 +323,25 @@ size_t ff_sr_moments_workspace_bytes(int64_t B, int P);
 int ff_sr_moments(void* stream, int64_t B, int P, const double* scores, const double* eloc, const double* e_mean,
                   double* sums, void* workspace);
 int ff_sr_finish(void* stream, int P, const double* sums, double* fisher, double* obar, double* grad);
+/* The same for walkers of SEVERAL many-body states (BetaVMC: the joint p(n, x) = mu_n p_n(x)); 1 <= nstates <= 65536 (ABI 110).
+ * walker_state (B, int32) MUST be sorted ascending, as for ff_beta_state_partials: unsorted input is undefined (memory-safe; a state
+ * outside [0, nstates) enters no per-state sum and puts NaN into g_sum).  mean_e (nstates, DEVICE) is ff_beta_finish's baseline.
+ *   sums = [ S_raw = sum_b O_b O_b^T (P*P) | o_state[n] = sum_{b in n} O_b (nstates*P) |
+ *            g_sum = sum_b O_b (eloc[b] - mean_e[walker_state[b]]) (P) | c_state[n] = walkers in state n, as doubles (nstates) ]
+ * RAW sums, additive over any split of the batch (also inside a state): ranks add them with one all-reduce.  Deterministic as
+ * ff_sr_moments is (S_raw: the same kernel body; per state: walker order inside a chunk of 2048, chunk order across chunks; no
+ * floating-point atomics; independent of the grid).  A NaN row makes the sums it enters NaN.  B = 0 gives zeros.
+ * ff_sr_state_finish turns the (all-reduced) sums into the pooled within-state scatter
+ *   fisher = (1/B) [S_raw - sum_{n: c_n > 0} o_n o_n^T / c_n]  (P,P; exactly symmetric; the correction is the Gram matrix of the rows
+ *            o_n / sqrt(c_n), on the matrix cores)      obar_state[n] = o_n / c_n (nstates,P; 0 for an empty state)
+ *   grad = g_sum / B                                    with B = sum_n c_n (zero gives NaN).
+ * One workspace serves both calls (the query's size; contents need not survive between them).  Refusals carry "ff_sr: ..." and
+ * launch nothing; the query returns 0 outside the limits. */
+size_t ff_sr_state_moments_workspace_bytes(int64_t B, int P, int nstates);
+int ff_sr_state_moments(void* stream, int64_t B, int P, int nstates, const double* scores, const double* eloc,
+                        const int32_t* walker_state, const double* mean_e, double* sums, void* workspace);
+int ff_sr_state_finish(void* stream, int P, int nstates, const double* sums, double* fisher, double* obar_state, double* grad,
+                       void* workspace);
 
 /* ---- local energy (src/VMC.py:46-55 via src/utils.py:40-65) --------------------------------- */
 /* Two launches: (1) a fused per-walker Dormand-Prince pass integrating z, J = dz/dx, the x-Laplacian of z,

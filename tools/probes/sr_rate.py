@@ -3,7 +3,13 @@
       resource figure for resource figure; FERMIFLOW_LIB=<a build of the parent> runs the direct leg alone on that build,
   (b) ff_sr_moments in TFLOP/s (2 B P^2 flop) against the 78.6 TFLOP/s fp64 matrix peak, and the bytes its design moves (O once per panel pair + the partial tiles twice; no counter is read) against 8 B P,
   (c) one SR iteration against one Adam iteration.
-Device events, a warm-up, medians of alternating runs.  Prints one JSON line; python tools/probes/sr_rate.py [B] [reps]"""
+Device events, a warm-up, medians of alternating runs.  Prints one JSON line; python tools/probes/sr_rate.py [B] [reps]
+
+    python tools/probes/sr_rate.py beta [B] [reps]
+is the leg at config 3 (BetaFermionHO2D --beta 10 --nup 3 --boltzmann: 65 536 walkers, P = 300, 21 states):
+  (d) ff_sr_state_moments against ff_sr_moments -- the parent's kernel, unchanged -- on the same scores (extra work: the flush at
+      every change of state and (nchunks + nstates) P partials), and ff_sr_state_finish against ff_sr_finish,
+  (e) one BetaSR iteration against one Adam iteration."""
 import json
 import os
 import statistics
@@ -73,5 +79,45 @@ def main():
     print(json.dumps(out))
 
 
+def main_beta(argv):
+    B = int(argv[0]) if len(argv) > 0 else 65536
+    reps = int(argv[1]) if len(argv) > 1 else 7
+    dev = torch.device("cuda:0")
+    eta, mu = ff.MLP(1, 50), ff.MLP(1, 50)
+    eta.init_gaussian(1); mu.init_gaussian(2)
+    cnf = ff.CNF(ff.Backflow(eta, mu=mu), (0.0, 1.0))
+    model = ff.BetaVMC(10.0, 3, 0, 2.0, True, ff.HO2D(), ff.FreeFermion(device=dev), cnf, ff.CoulombPairPotential(0.5), sp_potential=ff.HO())
+    model.to(device=dev)
+    from fermiflow_amd.utils import make_adam
+    adam, sr = make_adam(model.parameters(), lr=1e-2), ff.BetaSR(model)
+    torch.manual_seed(0)
+
+    def iteration(opt):
+        model.sr = opt if opt is sr else None
+        gp, gt = model(B); opt.zero_grad(); gp.backward(); gt.backward(); opt.step()
+    for opt in (adam, sr, adam, sr):
+        iteration(opt)
+    O, e, ws, Ns = sr.scores, model.Eloc, model._ws, model.Nstates
+    P = O.shape[1]
+    me = torch.full((Ns,), e.mean().item(), dtype=torch.float64, device=dev)
+    plain = lambda: native.sr_moments(O, e, me)
+    state = lambda: native.sr_state_moments(O, e, ws, me, Ns)
+    sp, ss = plain(), state()
+    fplain = lambda: native.sr_finish(sp, P)
+    fstate = lambda: native.sr_state_finish(ss, P, Ns)
+    fplain(); fstate()
+    t = {k: [] for k in ("plain", "state", "fplain", "fstate", "adam", "sr")}
+    for _ in range(reps):      # alternating
+        t["plain"].append(timed(plain)); t["state"].append(timed(state))
+        t["fplain"].append(timed(fplain)); t["fstate"].append(timed(fstate))
+    for _ in range(reps):
+        t["adam"].append(timed(lambda: iteration(adam))); t["sr"].append(timed(lambda: iteration(sr)))
+    m = {k: statistics.median(v) for k, v in t.items()}
+    print(json.dumps({"B": B, "P": P, "nstates": Ns, "reps": reps, "moments_ms": m["plain"], "state_moments_ms": m["state"],
+                      "state_over_plain": m["state"] / m["plain"], "finish_ms": m["fplain"], "state_finish_ms": m["fstate"],
+                      "adam_iteration_ms": m["adam"], "betasr_iteration_ms": m["sr"],
+                      "spread_state_moments_ms": [min(t["state"]), max(t["state"])], "spread_moments_ms": [min(t["plain"]), max(t["plain"])]}))
+
+
 if __name__ == "__main__":
-    main()
+    main_beta(sys.argv[2:]) if len(sys.argv) > 1 and sys.argv[1] == "beta" else main()
