@@ -329,7 +329,9 @@ class _Sweep:
 
     def _std(self, key):
         n = self._n_global
-        return (self._dev[key + "_ss"] / (n - 1)).sqrt().item() if n > 1 else float("nan")
+        # (the kernels clamp their centred sums of squares at zero; sums restored from an older checkpoint may carry a rounding-sized
+        # negative one -- NaN stays NaN)
+        return (self._dev[key + "_ss"] / (n - 1)).clamp_min(0.0).sqrt().item() if n > 1 else float("nan")
 
     # sweep state that a checkpoint must carry for the next iteration to repeat exactly (torch.nn.Module hooks: the
     # values travel inside state_dict() under "_extra_state")

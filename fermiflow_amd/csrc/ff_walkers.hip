@@ -461,7 +461,8 @@ ff_energy_sums_kernel(int64_t B, const double* __restrict__ e, const double* __r
 FF_D void ff_energy_finish_values(const double* sums, double shift, double n, double* est) {
   const double d = sums[0] / n;                       // E - c
   est[0] = shift + d;
-  est[1] = sums[1] - sums[0] * d;                     // sum (e - E)^2 = sum (e - c)^2 - n (E - c)^2
+  const double ss = sums[1] - sums[0] * d;            // sum (e - E)^2 = sum (e - c)^2 - n (E - c)^2
+  est[1] = ss < 0.0 ? 0.0 : ss;                       // (a difference: rounding can leave it below zero; NaN stays NaN)
   est[2] = (sums[3] - d * sums[2]) / n;               // mean(logp (e - E))
 }
 __global__ void __launch_bounds__(FF_EST_THREADS)
@@ -636,21 +637,28 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
   for (int s = t; s < Ns; s += nt) z += exp(logits[s] - mx);
   const double lz = mx + log(block_sum(z));
   // per state: sums over the slices in a fixed order
-  double sF = 0.0, sCE = 0.0, sCC = 0.0, sS = 0.0, sSa = 0.0;
+  const double c0 = ff_finite_shift(shift_dev[0]);
+  double sF = 0.0, sCE = 0.0, sCC = 0.0, sS = 0.0, sSa = 0.0, sD = 0.0;
   for (int s = t; s < Ns; s += nt) {
     double se = 0.0, cnt = 0.0;
     for (int k = 0; k < FF_SS_K; k++) { const double* o = part + ((size_t)s * FF_SS_K + k) * 4; se += o[0]; cnt += o[1]; }
     const double lp = logits[s] - lz, c = lp / beta;
+    const double sec = se - cnt * c0;                                           // sum over the state of (e - c0)
     logp_all[s] = lp;
     mean_e[s] = se / fmax(cnt, 1.0);
-    sF += se + cnt * c; sCE += c * se; sCC += cnt * c * c; sS += cnt * lp; sSa += lp * exp(lp);
+    sF += se + cnt * c; sCE += c * sec; sCC += cnt * c * c; sS += cnt * lp; sSa += lp * exp(lp); sD += sec + cnt * c;
   }
-  sF = block_sum(sF); sCE = block_sum(sCE); sCC = block_sum(sCC); sS = block_sum(sS); sSa = block_sum(sSa);
-  const double c0 = ff_finite_shift(shift_dev[0]), d = buf[0] / n;            // E - c
+  sF = block_sum(sF); sCE = block_sum(sCE); sCC = block_sum(sCC); sS = block_sum(sS); sSa = block_sum(sSa); sD = block_sum(sD);
+  const double d = buf[0] / n;                                                  // E - c
   const double E = c0 + d, Ess = buf[1] - buf[0] * d, F = sF / n;
-  // sum f^2 = sum e^2 + 2 sum_s c_s sum_e(s) + sum_s cnt_s c_s^2,  sum e^2 = sum (e - c)^2 + 2 c sum (e - c) + n c^2
-  const double se2 = buf[1] + 2.0 * c0 * buf[0] + n * c0 * c0;
-  const double Fss = se2 + 2.0 * sCE + sCC - n * F * F;
+  // sum (f - F)^2 about the shift, like E's: with g = f - c0 = (e - c0) + c_s,  sum g^2 = sum (e - c0)^2 + 2 sum_s c_s sum_s(e - c0)
+  // + sum_s cnt_s c_s^2  and  sum (f - F)^2 = sum g^2 - n (F - c0)^2.  (Formed from the moments about zero the difference of two
+  // numbers n E^2 lost n E^2 eps, 3e-7 at 65 536 walkers, either sign, wherever the shift.)  Not every trace of E is gone: the
+  // per-state sums arrive about zero, sum_s(e - c0) = se - cnt c0 cancels two numbers of size cnt E, and the rounding se already
+  // carries -- a few cnt |E| eps -- stays.  F - c0 is taken from the same per-state sums, so that this residual enters through
+  // c_s - (F - c0) only: about 2 |c_s - (F - c0)| n |E| eps, linear in E (1e-10 where the old form lost 3e-7).
+  const double dF = sD / n;
+  const double Fss = buf[1] + 2.0 * sCE + sCC - sD * dF;
   double sG = 0.0, sC = 0.0, sT = 0.0;
   for (int s = t; s < Ns; s += nt) {
     double se = 0.0, cnt = 0.0, sl = 0.0, sle = 0.0;
@@ -664,7 +672,7 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
   sG = block_sum(sG); sC = block_sum(sC); sT = block_sum(sT);
   for (int s = t; s < Ns; s += nt) gphi[s] -= exp(logits[s] - lz) * sC;
   if (t == 0) {
-    est[0] = E; est[1] = Ess; est[2] = F; est[3] = Fss; est[4] = -sS / n; est[5] = -sSa; est[6] = sG; est[7] = sT / n;
+    est[0] = E; est[1] = Ess < 0.0 ? 0.0 : Ess; est[2] = F; est[3] = Fss < 0.0 ? 0.0 : Fss; est[4] = -sS / n; est[5] = -sSa; est[6] = sG; est[7] = sT / n;
   }
 }
 

@@ -763,3 +763,15 @@ def test_kernel_plan_reproduces_the_recorded_routing():
         want = 0.25 if (n, d) == (1, 3) else min(0.25, max(0.06, 1.0 - 0.65 ** (1.0 / G)))
         assert s._h_shrink_at == want, (n, d, s._h_shrink_at, want)
         assert G == PLAN_TABLE[("eloc", n, d)][1] or (n, d) == (1, 3)
+
+
+def test_std_of_a_negative_sum_of_squares_is_zero_and_nan_stays_nan():
+    """VMC._std clamps like the kernels: all-reduced sums restored from an older checkpoint may carry a rounding-sized negative centred
+    sum of squares (sqrt of it was a NaN E_std / F_std); a NaN sum stays NaN"""
+    import math
+    from fermiflow_amd.VMC import _Sweep
+    sw = _Sweep.__new__(_Sweep)
+    sw._n_global = 1000
+    sw._dev = {"E_ss": torch.tensor(-1.98e-9, dtype=torch.float64), "F_ss": torch.tensor(float("nan"), dtype=torch.float64),
+               "S_ss": torch.tensor(999.0, dtype=torch.float64)}
+    assert sw._std("E") == 0.0 and math.isnan(sw._std("F")) and sw._std("S") == 1.0

@@ -9,6 +9,7 @@ import pytest
 
 from oracle import oracle as O
 from tests.common import mcmc_noise_from_seed, net_arrays, cnf_param_grads, gsvmc_param_grads
+from tests.estimator_ref import rule
 from tests.hostsim import simlib as S
 
 
@@ -930,22 +931,6 @@ def test_one_launch_estimator_and_schedule_with_mean():
         # with < 5 % grow by 1.02 if 70 % of their voters (without an interval: every walker) accepted a step of the plan one shorter
         # (without an interval: 1.25 x the opening step); within [0.25, 1]; classes with fewer than 64 walkers and walkers without a
         # step keep theirs
-        def rule(tab, cls, hs, he, interval, shrink_at=0.10):
-            want = tab.copy()
-            ok = (he > 0) & (hs > 0)
-            if interval > 0:
-                k = np.rint(interval / np.where(hs > 0, hs, 1.0))
-                vote = ok & (k >= 3)
-                yes = vote & (he >= 0.999 * interval / np.maximum(k - 1, 1))
-            else:
-                vote, yes = ok, ok & (he >= 1.25 * hs)
-            for c in range(32):
-                m = cls == c
-                n_c, r_c, v_c, y_c = int((m & ok).sum()), int((m & ok & (he < 0.999 * hs)).sum()), int((m & vote).sum()), int((m & yes).sum())
-                if n_c >= 64:
-                    f = 0.93 if r_c / n_c > shrink_at else (1.02 if (r_c / n_c < 0.5 * shrink_at and v_c >= 16 and y_c >= 0.7 * v_c) else 1.0)
-                    want[c] = min(1.0, max(0.25, tab[c] * f))
-            return want
         tab = np.where(np.arange(32) <= 6, 0.9, 0.6)
         o2, hm2, hs, tab1 = S.walker_schedule(cost, h, tab)
         assert (o2 == order).all() and hm2 == hm and (tab1 == tab).all()
