@@ -1,4 +1,4 @@
-"""ctypes binding of libfermiflow_hip.so (the C ABI declared in include/fermiflow.h).
+"""ctypes binding of libfermiflow_hip.so (the C ABI declared in include/fermiflow.h; its structs and signatures: _abi.py).
 
 The library is the product: if it is missing, or a tensor is not a contiguous fp64 CUDA tensor, the
 calls raise -- there is no CPU or PyTorch fallback anywhere in this package.
@@ -8,40 +8,13 @@ import os
 
 import torch
 
+from ._abi import ABI_VERSION, SIGNATURES, FFKernelPlanInfo, FFNet, FFOde, bind, ode_struct  # noqa: F401 (the structs are part of this module's surface)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FERMIFLOW_LIB") or os.path.join(_HERE, "libfermiflow_hip.so")   # env: A/B builds in tools/
 _LIB = None
 
-ABI_VERSION = 110      # ff_version() of the library this binding was written against (include/fermiflow.h)
-
-SYMBOLS = [
-    "ff_version", "ff_last_error", "ff_fermion_states", "ff_slater_logabsdet_fwd", "ff_slater_logabsdet_bwd", "ff_logprob",
-    "ff_mcmc_sample_noise", "ff_mcmc_sample", "ff_mcmc_continue", "ff_rng_fill", "ff_mlp_eval", "ff_backflow_v_div", "ff_potential", "ff_radial_table_bytes", "ff_radial_table_build",
-    "ff_cnf_generate", "ff_cnf_generate_frames", "ff_cnf_delta_logp", "ff_cnf_adjoint_workspace_bytes", "ff_cnf_adjoint", "ff_cnf_adjoint_energy", "ff_reduce_energy", "ff_energy_finish", "ff_stream_delay",
-    "ff_eloc_workspace_bytes", "ff_eloc", "ff_eloc_sensitivities", "ff_eloc_finish", "ff_reduce_moments", "ff_state_sums", "ff_beta_buffer_doubles", "ff_beta_state_partials", "ff_beta_finish", "ff_logprob3d", "ff_mcmc_sample_noise3d", "ff_mcmc_sample3d", "ff_eloc_finish3d", "ff_backflow_v_div_f32", "ff_walker_order_workspace_bytes", "ff_walker_order", "ff_set_kernel_family", "ff_set_sens_precision", "ff_shutdown", "ff_walker_order_mean", "ff_energy_estimate_workspace_bytes", "ff_energy_estimate", "ff_mlp_eval_nd", "ff_backflow_vjp", "ff_eloc_nd", "ff_eloc_nd_workspace_bytes", "ff_rng_fill3d", "ff_walker_schedule", "ff_scale_counts", "ff_comm_unique_id", "ff_comm_init", "ff_comm_allreduce", "ff_comm_destroy", "ff_adam_step",
-    "ff_observe_buffer_bytes", "ff_observe_accumulate", "ff_kernel_plan",
-    "ff_cnf_adjoint_scores_workspace_bytes", "ff_cnf_adjoint_scores", "ff_sr_moments_workspace_bytes", "ff_sr_moments", "ff_sr_finish",
-    "ff_sr_state_moments_workspace_bytes", "ff_sr_state_moments", "ff_sr_state_finish",
-]
-
-
-class FFNet(C.Structure):
-    _fields_ = [("He", C.c_int32), ("ew1", C.c_void_p), ("eb1", C.c_void_p), ("ew2", C.c_void_p),
-                ("Hm", C.c_int32), ("mw1", C.c_void_p), ("mb1", C.c_void_p), ("mw2", C.c_void_p),
-                ("radial_table", C.c_void_p)]
-
-
-class FFOde(C.Structure):
-    _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("rtol", C.c_double), ("atol", C.c_double),
-                ("max_steps", C.c_int32), ("walker_cost", C.c_void_p), ("walker_order", C.c_void_p),
-                ("walker_h_init", C.c_void_p), ("walker_h_scale", C.c_double), ("walker_h_out", C.c_void_p),
-                ("walker_class", C.c_void_p), ("sens_tol", C.c_double), ("walker_h_scale_loose", C.c_double), ("sens_tol_class", C.c_int32),
-                ("walker_h_uniform", C.c_int32), ("heavy_class", C.c_int32), ("heavy_tol", C.c_double), ("sum_weight", C.c_double),
-                ("compact_finish", C.c_int32), ("after_main_event", C.c_void_p), ("walker_h_equal", C.c_int32)]
-
-
-class FFKernelPlanInfo(C.Structure):
-    _fields_ = [("family", C.c_int32), ("group", C.c_int32), ("round", C.c_int64)]
+SYMBOLS = list(SIGNATURES)
 
 
 def lib():
@@ -57,19 +30,7 @@ def lib():
             v, _LIB = _LIB.ff_version(), None
             raise RuntimeError(f"{LIB_PATH} has ABI version {v}, this binding expects {ABI_VERSION}: rebuild "
                                "(python -c 'import __graft_entry__ as g; g.build()')")
-        _LIB.ff_last_error.restype = C.c_char_p
-        _LIB.ff_eloc_workspace_bytes.restype = C.c_size_t
-        _LIB.ff_eloc_nd_workspace_bytes.restype = C.c_size_t
-        _LIB.ff_cnf_adjoint_workspace_bytes.restype = C.c_size_t
-        _LIB.ff_radial_table_bytes.restype = C.c_size_t
-        _LIB.ff_walker_order_workspace_bytes.restype = C.c_size_t
-        _LIB.ff_fermion_states.restype = C.c_int64
-        _LIB.ff_beta_buffer_doubles.restype = C.c_size_t
-        _LIB.ff_energy_estimate_workspace_bytes.restype = C.c_size_t
-        _LIB.ff_observe_buffer_bytes.restype = C.c_size_t
-        for name in ("ff_cnf_adjoint_scores_workspace_bytes", "ff_sr_moments_workspace_bytes", "ff_sr_state_moments_workspace_bytes"):
-            if hasattr(_LIB, name):      # (FERMIFLOW_LIB may name an A/B build of an earlier commit with the same ABI version: tools/probes/sr_rate.py)
-                getattr(_LIB, name).restype = C.c_size_t
+        bind(_LIB)
     return _LIB
 
 
@@ -101,14 +62,6 @@ def ptr(t):
 
 def stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def i64(v):
-    return C.c_int64(int(v))
-
-
-def f64(v):
-    return C.c_double(float(v))
 
 
 RADIAL_MODE = os.environ.get("FERMIFLOW_RADIAL", "table")   # "table" (default) | "exact": how the ODE kernels evaluate eta, mu
@@ -161,7 +114,9 @@ def ode(t0, t1, rtol, atol, max_steps=0, walker_cost=None, walker_order=None, wa
         if tns is not None and not (tns.dtype == dt and tns.is_contiguous() and tns.is_cuda):
             raise ValueError(f"{name} must be a contiguous {dt} device tensor")
     p = lambda t: t.data_ptr() if t is not None else None
-    return FFOde(float(t0), float(t1), float(rtol), float(atol), int(max_steps), p(walker_cost), p(walker_order),
-                 p(walker_h_init), float(walker_h_scale), p(walker_h_out), p(walker_class), float(sens_tol), float(walker_h_scale_loose),
-                 int(sens_tol_class), int(bool(walker_h_uniform)), int(heavy_class), float(heavy_tol), float(sum_weight), int(bool(compact_finish)),
-                 (int(after_main_event.cuda_event) or None) if after_main_event is not None else None, int(bool(walker_h_equal)))
+    return ode_struct(t0=t0, t1=t1, rtol=rtol, atol=atol, max_steps=int(max_steps), walker_cost=p(walker_cost), walker_order=p(walker_order),
+                      walker_h_init=p(walker_h_init), walker_h_scale=walker_h_scale, walker_h_out=p(walker_h_out), walker_class=p(walker_class),
+                      sens_tol=sens_tol, walker_h_scale_loose=walker_h_scale_loose, sens_tol_class=int(sens_tol_class),
+                      walker_h_uniform=bool(walker_h_uniform), heavy_class=int(heavy_class), heavy_tol=heavy_tol, sum_weight=sum_weight,
+                      compact_finish=bool(compact_finish), walker_h_equal=bool(walker_h_equal),
+                      after_main_event=(int(after_main_event.cuda_event) or None) if after_main_event is not None else None)

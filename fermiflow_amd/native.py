@@ -41,7 +41,7 @@ def kernel_plan(call, n, dim, cus=256):
     the kernel the library's default routing gives `call` (one of PLAN_CALLS; "_fb": the direct kernel behind the table kernel) at
     n particles in `dim` dimensions.  A pure function of its arguments: no GPU needed.  NotImplementedError for a shape no kernel serves."""
     out = L.FFKernelPlanInfo()
-    L.check(L.lib().ff_kernel_plan(PLAN_CALLS.index(call), int(n), int(dim), L.i64(cus), C.byref(out)), "ff_kernel_plan")
+    L.check(L.lib().ff_kernel_plan(PLAN_CALLS.index(call), int(n), int(dim), int(cus), C.byref(out)), "ff_kernel_plan")
     return PLAN_FAMILIES[out.family], int(out.group), int(out.round)
 
 
@@ -59,8 +59,7 @@ def slater_fwd(table, x, walker_state=None):
     x = L.dev(x, name="x")
     B, n = x.shape[0], x.shape[1]
     out = torch.empty(B, dtype=torch.float64, device=x.device)
-    L.check(L.lib().ff_slater_logabsdet_fwd(L.stream(), L.i64(B), n, L.ptr(table), L.ptr(_state(walker_state)), L.ptr(x),
-                                            L.ptr(out)), "ff_slater_logabsdet_fwd")
+    L.check(L.lib().ff_slater_logabsdet_fwd(L.stream(), B, n, L.ptr(table), L.ptr(_state(walker_state)), L.ptr(x), L.ptr(out)), "ff_slater_logabsdet_fwd")
     return out
 
 
@@ -68,7 +67,7 @@ def slater_bwd(table, x, grad_out, walker_state=None):
     x = L.dev(x, name="x"); go = L.dev(grad_out, name="grad_out")
     B, n = x.shape[0], x.shape[1]
     gx = torch.empty_like(x)
-    L.check(L.lib().ff_slater_logabsdet_bwd(L.stream(), L.i64(B), n, L.ptr(table), L.ptr(_state(walker_state)), L.ptr(x),
+    L.check(L.lib().ff_slater_logabsdet_bwd(L.stream(), B, n, L.ptr(table), L.ptr(_state(walker_state)), L.ptr(x),
                                             L.ptr(go), L.ptr(gx)), "ff_slater_logabsdet_bwd")
     return gx
 
@@ -79,7 +78,7 @@ def logprob(tab_up, tab_dn, nup, ndn, x, walker_state=None, derivs=False):
     logp = torch.empty(B, dtype=torch.float64, device=x.device)
     grad = torch.empty_like(x) if derivs else None
     lap = torch.empty(B, dtype=torch.float64, device=x.device) if derivs else None
-    L.check(L.lib().ff_logprob(L.stream(), L.i64(B), nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
+    L.check(L.lib().ff_logprob(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
                                L.ptr(x), L.ptr(logp), L.ptr(grad), L.ptr(lap)), "ff_logprob")
     return (logp, grad, lap) if derivs else logp
 
@@ -89,9 +88,8 @@ def mcmc_sample(tab_up, tab_dn, nup, ndn, B, steps, tau, seed, device, walker_of
     x = torch.empty(B, n, 2, dtype=torch.float64, device=device)
     logp = torch.empty(B, dtype=torch.float64, device=device)
     cnt = torch.empty(B, dtype=torch.int32, device=device)
-    L.check(L.lib().ff_mcmc_sample(L.stream(), L.i64(B), nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
-                                   int(steps), L.f64(tau), C.c_uint64(int(seed) & (2**64 - 1)), L.i64(walker_offset),
-                                   L.ptr(x), L.ptr(logp), L.ptr(cnt)), "ff_mcmc_sample")
+    L.check(L.lib().ff_mcmc_sample(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), int(steps), tau,
+                                   int(seed) & (2**64 - 1), int(walker_offset), L.ptr(x), L.ptr(logp), L.ptr(cnt)), "ff_mcmc_sample")
     return x, logp, cnt
 
 
@@ -102,9 +100,8 @@ def mcmc_continue(tab_up, tab_dn, nup, ndn, x_init, steps, tau, seed, walker_off
     x = torch.empty_like(x0)
     logp = torch.empty(B, dtype=torch.float64, device=x0.device)
     cnt = torch.empty(B, dtype=torch.int32, device=x0.device)
-    L.check(L.lib().ff_mcmc_continue(L.stream(), L.i64(B), nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
-                                     int(steps), L.f64(tau), C.c_uint64(int(seed) & (2**64 - 1)), L.i64(walker_offset),
-                                     L.ptr(x0), L.ptr(x), L.ptr(logp), L.ptr(cnt)), "ff_mcmc_continue")
+    L.check(L.lib().ff_mcmc_continue(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), int(steps), tau,
+                                     int(seed) & (2**64 - 1), int(walker_offset), L.ptr(x0), L.ptr(x), L.ptr(logp), L.ptr(cnt)), "ff_mcmc_continue")
     return x, logp, cnt
 
 
@@ -114,9 +111,8 @@ def mcmc_sample_noise(tab_up, tab_dn, nup, ndn, g0, g, u, tau=0.1, walker_state=
     x = torch.empty_like(g0)
     logp = torch.empty(B, dtype=torch.float64, device=g0.device)
     acc = torch.empty(steps, B, dtype=torch.uint8, device=g0.device)
-    L.check(L.lib().ff_mcmc_sample_noise(L.stream(), L.i64(B), nup, ndn, L.ptr(tab_up), L.ptr(tab_dn),
-                                         L.ptr(_state(walker_state)), int(steps), L.f64(tau), L.ptr(g0), L.ptr(g), L.ptr(u),
-                                         L.ptr(x), L.ptr(logp), L.ptr(acc)), "ff_mcmc_sample_noise")
+    L.check(L.lib().ff_mcmc_sample_noise(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), int(steps), tau, L.ptr(g0),
+                                         L.ptr(g), L.ptr(u), L.ptr(x), L.ptr(logp), L.ptr(acc)), "ff_mcmc_sample_noise")
     return x, logp, acc
 
 
@@ -126,8 +122,7 @@ def rng_fill(B, n, steps, seed, device, walker_offset=0, dim=2):
     g = torch.empty(steps, B, n, dim, dtype=torch.float64, device=device)
     u = torch.empty(steps, B, dtype=torch.float64, device=device)
     fn, name = (L.lib().ff_rng_fill, "ff_rng_fill") if dim == 2 else (L.lib().ff_rng_fill3d, "ff_rng_fill3d")
-    L.check(fn(L.stream(), L.i64(B), n, int(steps), C.c_uint64(int(seed) & (2**64 - 1)), L.i64(walker_offset),
-               L.ptr(g0), L.ptr(g), L.ptr(u)), name)
+    L.check(fn(L.stream(), B, n, int(steps), int(seed) & (2**64 - 1), int(walker_offset), L.ptr(g0), L.ptr(g), L.ptr(u)), name)
     return g0, g, u
 
 
@@ -136,8 +131,7 @@ def mlp_eval(w1, b1, w2, r, need_grad=True):
     w1, b1, w2 = L.dev(w1.reshape(-1)), L.dev(b1), L.dev(w2.reshape(-1))
     val = torch.empty_like(r)
     dval = torch.empty_like(r) if need_grad else None
-    L.check(L.lib().ff_mlp_eval(L.stream(), L.i64(r.numel()), b1.numel(), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(r),
-                                L.ptr(val), L.ptr(dval)), "ff_mlp_eval")
+    L.check(L.lib().ff_mlp_eval(L.stream(), r.numel(), b1.numel(), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(r), L.ptr(val), L.ptr(dval)), "ff_mlp_eval")
     return val, dval
 
 
@@ -148,8 +142,7 @@ def mlp_eval_nd(w1, b1, w2, x, need_val=True, need_grad=False):
     w1, b1, w2 = L.dev(w1.reshape(-1, Din)), L.dev(b1), L.dev(w2.reshape(-1))
     val = torch.empty(N, dtype=torch.float64, device=x.device) if need_val else None
     grad = torch.empty_like(x) if need_grad else None
-    L.check(L.lib().ff_mlp_eval_nd(L.stream(), L.i64(N), int(Din), b1.numel(), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(x), L.ptr(val), L.ptr(grad)),
-            "ff_mlp_eval_nd")
+    L.check(L.lib().ff_mlp_eval_nd(L.stream(), N, int(Din), b1.numel(), L.ptr(w1), L.ptr(b1), L.ptr(w2), L.ptr(x), L.ptr(val), L.ptr(grad)), "ff_mlp_eval_nd")
     return val, grad
 
 
@@ -160,7 +153,7 @@ def backflow_vjp(net, x, w=None, need_gdiv=False):
     w = L.dev(w, name="w") if w is not None else None
     Aw = torch.empty_like(x) if w is not None else None
     gd = torch.empty_like(x) if need_gdiv else None
-    L.check(L.lib().ff_backflow_vjp(L.stream(), L.i64(B), n, d, net.ref(), L.ptr(x), L.ptr(w), L.ptr(Aw), L.ptr(gd)), "ff_backflow_vjp")
+    L.check(L.lib().ff_backflow_vjp(L.stream(), B, n, d, net.ref(), L.ptr(x), L.ptr(w), L.ptr(Aw), L.ptr(gd)), "ff_backflow_vjp")
     return Aw, gd
 
 
@@ -169,8 +162,7 @@ def backflow_v_div(net, x, need_v=True, need_div=True):
     B, n, d = x.shape
     v = torch.empty_like(x) if need_v else None
     div = torch.empty(B, dtype=torch.float64, device=x.device) if need_div else None
-    L.check(L.lib().ff_backflow_v_div(L.stream(), L.i64(B), n, d, net.ref(), L.ptr(x), L.ptr(v), L.ptr(div)),
-            "ff_backflow_v_div")
+    L.check(L.lib().ff_backflow_v_div(L.stream(), B, n, d, net.ref(), L.ptr(x), L.ptr(v), L.ptr(div)), "ff_backflow_v_div")
     return v, div
 
 
@@ -178,7 +170,7 @@ def potential(x, Z, use_ho):
     x = L.dev(x, name="x")
     B, n, d = x.shape
     V = torch.empty(B, dtype=torch.float64, device=x.device)
-    L.check(L.lib().ff_potential(L.stream(), L.i64(B), n, d, L.f64(Z), int(bool(use_ho)), L.ptr(x), L.ptr(V)), "ff_potential")
+    L.check(L.lib().ff_potential(L.stream(), B, n, d, Z, int(bool(use_ho)), L.ptr(x), L.ptr(V)), "ff_potential")
     return V
 
 
@@ -193,8 +185,7 @@ def cnf_generate(net, z, t0, t1, rtol, atol, want_stats=False, walker_cost=None,
     x = torch.empty_like(z)
     st = _stats(z.device, want_stats)
     o = L.ode(t0, t1, rtol, atol, walker_cost=walker_cost, walker_order=walker_order, **warm)
-    L.check(L.lib().ff_cnf_generate(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(z), L.ptr(x), L.ptr(st)),
-            "ff_cnf_generate")
+    L.check(L.lib().ff_cnf_generate(L.stream(), B, n, d, net.ref(), C.byref(o), L.ptr(z), L.ptr(x), L.ptr(st)), "ff_cnf_generate")
     return (x, st) if want_stats else x
 
 
@@ -207,8 +198,7 @@ def cnf_generate_frames(net, z, nframes, t0, t1, rtol, atol, walker_cost=None, w
     frames = torch.empty((max(nframes, 1), B, n, d), dtype=torch.float64, device=z.device)
     st = _stats(z.device, True)
     o = L.ode(t0, t1, rtol, atol, walker_cost=walker_cost, walker_order=walker_order, **warm)
-    L.check(L.lib().ff_cnf_generate_frames(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(z), nframes, L.ptr(frames), L.ptr(st)),
-            "ff_cnf_generate_frames")
+    L.check(L.lib().ff_cnf_generate_frames(L.stream(), B, n, d, net.ref(), C.byref(o), L.ptr(z), nframes, L.ptr(frames), L.ptr(st)), "ff_cnf_generate_frames")
     return frames, st
 
 
@@ -219,8 +209,7 @@ def cnf_delta_logp(net, x, t0, t1, rtol, atol, want_stats=False, walker_cost=Non
     dl = torch.empty(B, dtype=torch.float64, device=x.device)
     st = _stats(x.device, want_stats)
     o = L.ode(t0, t1, rtol, atol, walker_cost=walker_cost, walker_order=walker_order, **warm)
-    L.check(L.lib().ff_cnf_delta_logp(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(x), L.ptr(z), L.ptr(dl),
-                                      L.ptr(st)), "ff_cnf_delta_logp")
+    L.check(L.lib().ff_cnf_delta_logp(L.stream(), B, n, d, net.ref(), C.byref(o), L.ptr(x), L.ptr(z), L.ptr(dl), L.ptr(st)), "ff_cnf_delta_logp")
     return (z, dl, st) if want_stats else (z, dl)
 
 
@@ -236,7 +225,7 @@ def cnf_adjoint(net, y_start, a_z, a_d, t_from, t_to, rtol, atol, need_gx=True, 
     B, n, d = y.shape
     gx = torch.empty_like(y) if need_gx else None
     gp = torch.empty(net.nparams, dtype=torch.float64, device=y.device)
-    nbytes = L.lib().ff_cnf_adjoint_workspace_bytes(L.i64(B), n, d, net.He, net.Hm)
+    nbytes = L.lib().ff_cnf_adjoint_workspace_bytes(B, n, d, net.He, net.Hm)
     ws = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=y.device)
     st = _stats(y.device, want_stats)
     o = L.ode(t_from, t_to, rtol, atol, walker_cost=walker_cost, walker_order=walker_order, **warm)
@@ -244,10 +233,10 @@ def cnf_adjoint(net, y_start, a_z, a_d, t_from, t_to, rtol, atol, need_gx=True, 
         e = L.dev(energy[0], name="eloc")
         mi = L.dev(energy[3], torch.int32, "mean_index") if len(energy) > 3 and energy[3] is not None else None
         em = L.dev(energy[1].reshape(-1) if mi is not None else energy[1].reshape(-1)[:1], name="e_mean")
-        L.check(L.lib().ff_cnf_adjoint_energy(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(y), L.ptr(a_z), L.ptr(e), L.ptr(em),
-                                              L.ptr(mi), L.f64(energy[2]), L.ptr(gx), L.ptr(gp), L.ptr(ws), L.ptr(st)), "ff_cnf_adjoint_energy")
+        L.check(L.lib().ff_cnf_adjoint_energy(L.stream(), B, n, d, net.ref(), C.byref(o), L.ptr(y), L.ptr(a_z), L.ptr(e), L.ptr(em),
+                                              L.ptr(mi), energy[2], L.ptr(gx), L.ptr(gp), L.ptr(ws), L.ptr(st)), "ff_cnf_adjoint_energy")
     else:
-        L.check(L.lib().ff_cnf_adjoint(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(y), L.ptr(a_z), L.ptr(a_d),
+        L.check(L.lib().ff_cnf_adjoint(L.stream(), B, n, d, net.ref(), C.byref(o), L.ptr(y), L.ptr(a_z), L.ptr(a_d),
                                        L.ptr(gx), L.ptr(gp), L.ptr(ws), L.ptr(st)), "ff_cnf_adjoint")
     return (gx, gp, st) if want_stats else (gx, gp)
 
@@ -260,12 +249,25 @@ def cnf_adjoint_scores(net, z_t0, glogp0, t_from, t_to, rtol, atol, want_stats=F
     scores = torch.empty((B, net.nparams), dtype=torch.float64, device=z.device)
     st = _stats(z.device, want_stats)
     o = L.ode(t_from, t_to, rtol, atol, walker_order=walker_order, **warm)
-    L.check(L.lib().ff_cnf_adjoint_scores(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(z), L.ptr(g0), L.ptr(scores), None,      # (no workspace: include/fermiflow.h)
+    L.check(L.lib().ff_cnf_adjoint_scores(L.stream(), B, n, d, net.ref(), C.byref(o), L.ptr(z), L.ptr(g0), L.ptr(scores), None,      # (no workspace: include/fermiflow.h)
                                           L.ptr(st)), "ff_cnf_adjoint_scores")
     return (scores, st) if want_stats else scores
 
 
-_SR_WS = {}      # (device, stream, B, P) -> workspace of ff_sr_moments (partial tiles; written in full by every call)
+def _cached_ws(cache, cap, alloc, device, sizes, nbytes):
+    """(key, workspace): the fp64 workspace `cache` holds for (device, the current stream of device, *sizes) -- a workspace belongs to
+    the stream its calls run on --, made by `alloc` (torch.zeros / torch.empty) from the size query `nbytes` (a callable) on a miss;
+    a cache that has grown past `cap` entries is emptied first."""
+    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream), *sizes)
+    ws = cache.get(key)
+    if ws is None:
+        if len(cache) > cap:
+            cache.clear()
+        ws = cache[key] = alloc(max(1, nbytes() // 8), dtype=torch.float64, device=device)
+    return key, ws
+
+
+_SR_WS = {}      # (device, stream, B, P[, nstates]) -> workspace of ff_sr_moments / ff_sr_state_* (partial tiles; written in full by every call)
 
 
 def sr_moments(scores, eloc, e_mean):
@@ -273,15 +275,9 @@ def sr_moments(scores, eloc, e_mean):
     then sr_finish.  e_mean: device tensor whose first element is E."""
     scores = L.dev(scores, name="scores"); e = L.dev(eloc, name="eloc"); em = L.dev(e_mean.reshape(-1)[:1], name="e_mean")
     B, P = scores.shape
-    nbytes = L.lib().ff_sr_moments_workspace_bytes(L.i64(B), int(P))
-    key = (str(scores.device), int(torch.cuda.current_stream(scores.device).cuda_stream), int(B), int(P))
-    ws = _SR_WS.get(key)
-    if ws is None:
-        if len(_SR_WS) > 16:
-            _SR_WS.clear()
-        ws = _SR_WS[key] = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=scores.device)
+    ws = _cached_ws(_SR_WS, 16, torch.empty, scores.device, (B, P), lambda: L.lib().ff_sr_moments_workspace_bytes(B, P))[1]
     sums = torch.empty(P * P + 2 * P + 2, dtype=torch.float64, device=scores.device)
-    L.check(L.lib().ff_sr_moments(L.stream(), L.i64(B), int(P), L.ptr(scores), L.ptr(e), L.ptr(em), L.ptr(sums), L.ptr(ws)), "ff_sr_moments")
+    L.check(L.lib().ff_sr_moments(L.stream(), B, P, L.ptr(scores), L.ptr(e), L.ptr(em), L.ptr(sums), L.ptr(ws)), "ff_sr_moments")
     return sums
 
 
@@ -305,20 +301,12 @@ def sr_state_moments(scores, eloc, walker_state, mean_e, nstates):
     ns = int(nstates)
     ws = _sr_state_ws(scores.device, B, P, ns)
     sums = torch.empty(P * P + ns * P + P + ns, dtype=torch.float64, device=scores.device)
-    L.check(L.lib().ff_sr_state_moments(L.stream(), L.i64(B), int(P), ns, L.ptr(scores), L.ptr(e), L.ptr(st), L.ptr(me), L.ptr(sums), L.ptr(ws)),
-            "ff_sr_state_moments")
+    L.check(L.lib().ff_sr_state_moments(L.stream(), B, P, ns, L.ptr(scores), L.ptr(e), L.ptr(st), L.ptr(me), L.ptr(sums), L.ptr(ws)), "ff_sr_state_moments")
     return sums
 
 
 def _sr_state_ws(device, B, P, nstates):
-    nbytes = L.lib().ff_sr_state_moments_workspace_bytes(L.i64(B), int(P), int(nstates))
-    key = (str(device), int(torch.cuda.current_stream(device).cuda_stream), int(B), int(P), int(nstates))
-    ws = _SR_WS.get(key)
-    if ws is None:
-        if len(_SR_WS) > 16:
-            _SR_WS.clear()
-        ws = _SR_WS[key] = torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=device)
-    return ws
+    return _cached_ws(_SR_WS, 16, torch.empty, device, (B, P, nstates), lambda: L.lib().ff_sr_state_moments_workspace_bytes(B, P, nstates))[1]
 
 
 def sr_state_finish(sums, P, nstates):
@@ -347,13 +335,13 @@ def eloc(tab_up, tab_dn, nup, ndn, net, x, t0, t1, rtol, atol, Z, use_ho, walker
     B, n, d = x.shape[0], nup + ndn, x.shape[2]
     f = dict(dtype=torch.float64, device=x.device)
     M = n * d
-    full_bytes = L.lib().ff_eloc_workspace_bytes(L.i64(B), n, d)
+    full_bytes = L.lib().ff_eloc_workspace_bytes(B, n, d)
     if compact is None:
         compact = M > 24 and full_bytes > COMPACT_WORKSPACE_BYTES
     if two_pass and compact:
         raise ValueError("two_pass keeps the sensitivities in the workspace: not with compact=True")
     compact_layout = bool(compact) and M > 24       # ff_eloc_nd beyond 24 coordinates: z(t0) | Delta only (include/fermiflow.h)
-    nbytes = L.lib().ff_eloc_nd_workspace_bytes(L.i64(B), n, d, int(bool(compact))) if not two_pass else full_bytes
+    nbytes = L.lib().ff_eloc_nd_workspace_bytes(B, n, d, int(bool(compact))) if not two_pass else full_bytes
     ws = torch.empty(max(1, nbytes // 8), **f)
     # z(t0) and Delta stay where the sensitivity pass leaves them: views of the workspace (its documented head, include/fermiflow.h)
     # instead of two device-to-device copies per sweep
@@ -368,22 +356,19 @@ def eloc(tab_up, tab_dn, nup, ndn, net, x, t0, t1, rtol, atol, Z, use_ho, walker
     if not two_pass:
         # one call: the library fuses the finish into the sensitivity kernel where that kernel implements it (then the second
         # event of pass1_events closes the whole pass)
-        L.check(L.lib().ff_eloc_nd(L.stream(), L.i64(B), nup, ndn, int(d), L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), net.ref(),
-                                   C.byref(o), L.f64(Z), int(bool(use_ho)), L.ptr(x), L.ptr(out["logp"]), L.ptr(out["grad"]),
-                                   L.ptr(out["lap"]), L.ptr(out["V"]), L.ptr(out["eloc"]), None, None, L.ptr(out["glogp0"]), L.ptr(ws),
-                                   L.ptr(st)), "ff_eloc_nd")
+        L.check(L.lib().ff_eloc_nd(L.stream(), B, nup, ndn, int(d), L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), net.ref(), C.byref(o), Z,
+                                   int(bool(use_ho)), L.ptr(x), L.ptr(out["logp"]), L.ptr(out["grad"]), L.ptr(out["lap"]), L.ptr(out["V"]), L.ptr(out["eloc"]),
+                                   None, None, L.ptr(out["glogp0"]), L.ptr(ws), L.ptr(st)), "ff_eloc_nd")
         if pass1_events is not None:
             pass1_events[1].record()
     else:
-        L.check(L.lib().ff_eloc_sensitivities(L.stream(), L.i64(B), n, d, net.ref(), C.byref(o), L.ptr(x), L.ptr(ws), L.ptr(st)),
-                "ff_eloc_sensitivities")
+        L.check(L.lib().ff_eloc_sensitivities(L.stream(), B, n, d, net.ref(), C.byref(o), L.ptr(x), L.ptr(ws), L.ptr(st)), "ff_eloc_sensitivities")
         if pass1_events is not None:
             pass1_events[1].record()
         finish = L.lib().ff_eloc_finish3d if d == 3 else L.lib().ff_eloc_finish      # d = 3: HO3D orbital tables (csrc/ff_ho3d.hip)
-        L.check(finish(L.stream(), L.i64(B), nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
-                       L.f64(Z), int(bool(use_ho)), L.ptr(x), L.ptr(ws), L.ptr(out["logp"]), L.ptr(out["grad"]),
-                       L.ptr(out["lap"]), L.ptr(out["V"]), L.ptr(out["eloc"]), None,
-                       None, L.ptr(out["glogp0"])), "ff_eloc_finish")
+        L.check(finish(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), Z, int(bool(use_ho)), L.ptr(x), L.ptr(ws),
+                       L.ptr(out["logp"]), L.ptr(out["grad"]), L.ptr(out["lap"]), L.ptr(out["V"]), L.ptr(out["eloc"]), None, None, L.ptr(out["glogp0"])),
+                "ff_eloc_finish")
     if want_stats:
         out["stats"] = st
     return out
@@ -396,14 +381,13 @@ def walker_order(cost, hval=None):
     if cost.dtype != torch.int32 or not cost.is_cuda:
         raise ValueError("cost must be an int32 device tensor")
     order = torch.empty_like(cost)
-    ws = torch.empty(max(1, (L.lib().ff_walker_order_workspace_bytes(L.i64(cost.numel())) + 7) // 8), dtype=torch.float64, device=cost.device)
+    ws = torch.empty(max(1, (L.lib().ff_walker_order_workspace_bytes(cost.numel()) + 7) // 8), dtype=torch.float64, device=cost.device)
     if hval is None:
-        L.check(L.lib().ff_walker_order(L.stream(), L.i64(cost.numel()), L.ptr(cost), L.ptr(order), L.ptr(ws)), "ff_walker_order")
+        L.check(L.lib().ff_walker_order(L.stream(), cost.numel(), L.ptr(cost), L.ptr(order), L.ptr(ws)), "ff_walker_order")
         return order
     hval = L.dev(hval, name="hval")
     hmean = torch.empty(1, dtype=torch.float64, device=cost.device)
-    L.check(L.lib().ff_walker_order_mean(L.stream(), L.i64(cost.numel()), L.ptr(cost), L.ptr(order), L.ptr(ws), L.ptr(hval), L.ptr(hmean)),
-            "ff_walker_order_mean")
+    L.check(L.lib().ff_walker_order_mean(L.stream(), cost.numel(), L.ptr(cost), L.ptr(order), L.ptr(ws), L.ptr(hval), L.ptr(hmean)), "ff_walker_order_mean")
     return order, hmean
 
 
@@ -417,16 +401,15 @@ def walker_schedule(cost, hval, scale_in, scale_out, prev=None, interval=0.0, co
     order = torch.empty_like(cost)
     hs = torch.empty_like(hval)
     hmean = torch.empty(1, dtype=torch.float64, device=cost.device)
-    ws = torch.empty(max(1, (L.lib().ff_walker_order_workspace_bytes(L.i64(cost.numel())) + 7) // 8), dtype=torch.float64, device=cost.device)
+    ws = torch.empty(max(1, (L.lib().ff_walker_order_workspace_bytes(cost.numel()) + 7) // 8), dtype=torch.float64, device=cost.device)
     pc, ph, pe = prev if prev is not None else (None, None, None)
     if prev is not None and not (pc.numel() == ph.numel() == pe.numel() == cost.numel()):
         raise ValueError("walker_schedule: the previous pass must have this call's batch size")
     if counts is not None and not (counts.numel() == SCALE_COUNTS and counts.dtype == torch.float64 and counts.is_contiguous()
                                    and counts.is_cuda and counts.device == cost.device):
         raise ValueError(f"walker_schedule: counts must be the {SCALE_COUNTS} doubles of scale_counts, contiguous, on the walkers' device")
-    L.check(L.lib().ff_walker_schedule(L.stream(), L.i64(cost.numel()), L.ptr(cost), L.ptr(order), L.ptr(ws), L.ptr(hval), L.ptr(hmean),
-                                       L.ptr(scale_in), L.ptr(scale_out), L.ptr(pc), L.ptr(ph), L.ptr(pe), L.ptr(counts), L.f64(abs(float(interval))), L.ptr(hs),
-                                       L.f64(shrink_at)),
+    L.check(L.lib().ff_walker_schedule(L.stream(), cost.numel(), L.ptr(cost), L.ptr(order), L.ptr(ws), L.ptr(hval), L.ptr(hmean), L.ptr(scale_in),
+                                       L.ptr(scale_out), L.ptr(pc), L.ptr(ph), L.ptr(pe), L.ptr(counts), abs(float(interval)), L.ptr(hs), shrink_at),
             "ff_walker_schedule")
     return order, hmean, hs
 
@@ -438,8 +421,7 @@ def scale_counts(cost, hs, he, interval=0.0):
     """ff_scale_counts: 128 doubles [walkers by cost class | of them, first step rejected | planned for >= 3 equal steps of `interval` | of
     those, accepted a step of the plan one shorter] of a local-energy pass (this rank's shard)"""
     counts = torch.zeros(SCALE_COUNTS, dtype=torch.float64, device=cost.device)
-    L.check(L.lib().ff_scale_counts(L.stream(), L.i64(cost.numel()), L.ptr(cost), L.ptr(hs), L.ptr(he), L.f64(abs(float(interval))), L.ptr(counts)),
-            "ff_scale_counts")
+    L.check(L.lib().ff_scale_counts(L.stream(), cost.numel(), L.ptr(cost), L.ptr(hs), L.ptr(he), abs(float(interval)), L.ptr(counts)), "ff_scale_counts")
     return counts
 
 
@@ -450,8 +432,7 @@ def reduce_moments(e, shift=0.0, shift_dev=None, shift_dev_scale=1.0, out=None):
     out = torch.empty(2, dtype=torch.float64, device=e.device) if out is None else out
     if shift_dev is not None:
         shift_dev = L.dev(shift_dev.reshape(1), name="shift_dev")
-    L.check(L.lib().ff_reduce_moments(L.stream(), L.i64(e.numel()), L.ptr(e), L.f64(shift), L.ptr(shift_dev),
-                                      L.f64(shift_dev_scale), L.ptr(out)), "ff_reduce_moments")
+    L.check(L.lib().ff_reduce_moments(L.stream(), e.numel(), L.ptr(e), shift, L.ptr(shift_dev), shift_dev_scale, L.ptr(out)), "ff_reduce_moments")
     return out
 
 
@@ -460,20 +441,20 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_
     n = len(params)
     arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
     sizes = (C.c_int64 * n)(*[p.numel() for p in params])
-    L.check(L.lib().ff_adam_step(L.stream(), n, sizes, arr(params), arr(grads), arr(exp_avg), arr(exp_avg_sq), L.f64(lr), L.f64(beta1), L.f64(beta2),
-                                 L.f64(eps), L.f64(weight_decay), L.i64(step)), "ff_adam_step")
+    L.check(L.lib().ff_adam_step(L.stream(), n, sizes, arr(params), arr(grads), arr(exp_avg), arr(exp_avg_sq), lr, beta1, beta2,
+                                 eps, weight_decay, int(step)), "ff_adam_step")
 
 
 def stream_delay(microseconds):
     """ff_stream_delay on the current stream."""
-    L.check(L.lib().ff_stream_delay(L.stream(), L.f64(microseconds)), "ff_stream_delay")
+    L.check(L.lib().ff_stream_delay(L.stream(), microseconds), "ff_stream_delay")
 
 
 def reduce_energy(e, logp, shift_dev):
     """ff_reduce_energy: tensor [sum(e - c), sum((e - c)^2), sum(logp), sum(logp (e - c))], c = shift_dev[0] (device)."""
     e = L.dev(e, name="e"); logp = L.dev(logp, name="logp"); shift_dev = L.dev(shift_dev.reshape(1), name="shift_dev")
     out = torch.empty(4, dtype=torch.float64, device=e.device)
-    L.check(L.lib().ff_reduce_energy(L.stream(), L.i64(e.numel()), L.ptr(e), L.ptr(logp), L.ptr(shift_dev), L.ptr(out)), "ff_reduce_energy")
+    L.check(L.lib().ff_reduce_energy(L.stream(), e.numel(), L.ptr(e), L.ptr(logp), L.ptr(shift_dev), L.ptr(out)), "ff_reduce_energy")
     return out
 
 
@@ -486,16 +467,11 @@ def energy_estimate(e, logp, shift_dev, n_global):
     B = e.numel()
     # the workspace (last-workgroup counter + per-segment partials) is the caller's per call STREAM (include/fermiflow.h): two sweeps on
     # different streams of one device must not share it
-    key = (str(e.device), int(torch.cuda.current_stream(e.device).cuda_stream), B)
-    ws = _EST_WS.get(key)
-    if ws is None:
-        if len(_EST_WS) > 64:
-            _EST_WS.clear()
-        ws = _EST_WS[key] = torch.zeros(L.lib().ff_energy_estimate_workspace_bytes(L.i64(B)) // 8, dtype=torch.float64, device=e.device)
+    key, ws = _cached_ws(_EST_WS, 64, torch.zeros, e.device, (B,), lambda: L.lib().ff_energy_estimate_workspace_bytes(B))
     sums = torch.empty(4, dtype=torch.float64, device=e.device)
     est = torch.empty(3, dtype=torch.float64, device=e.device) if n_global else None
     try:
-        L.check(L.lib().ff_energy_estimate(L.stream(), L.i64(B), L.ptr(e), L.ptr(logp), L.ptr(shift_dev), L.i64(n_global), L.ptr(sums), L.ptr(est),
+        L.check(L.lib().ff_energy_estimate(L.stream(), B, L.ptr(e), L.ptr(logp), L.ptr(shift_dev), int(n_global), L.ptr(sums), L.ptr(est),
                                            L.ptr(ws)), "ff_energy_estimate")
     except Exception:
         _EST_WS.pop(key, None)      # a launch that did not run to its end may have left the counter non-zero: never reuse this workspace
@@ -507,7 +483,7 @@ def energy_finish(sums4, shift_dev, n_global):
     """ff_energy_finish: tensor [E, sum((e - E)^2), mean(logp (e - E))] from the (all-reduced) sums of reduce_energy."""
     sums4 = L.dev(sums4, name="sums4"); shift_dev = L.dev(shift_dev.reshape(1), name="shift_dev")
     out = torch.empty(3, dtype=torch.float64, device=sums4.device)
-    L.check(L.lib().ff_energy_finish(L.stream(), L.ptr(sums4), L.ptr(shift_dev), L.i64(n_global), L.ptr(out)), "ff_energy_finish")
+    L.check(L.lib().ff_energy_finish(L.stream(), L.ptr(sums4), L.ptr(shift_dev), int(n_global), L.ptr(out)), "ff_energy_finish")
     return out
 
 
@@ -518,8 +494,7 @@ def beta_buffer(nstates, device):
 
 def beta_state_partials(e, logp, walker_state, nstates, buf):
     e = L.dev(e, name="e"); logp = L.dev(logp, name="logp"); ws = L.dev(walker_state, torch.int32, "walker_state")
-    L.check(L.lib().ff_beta_state_partials(L.stream(), L.i64(e.numel()), int(nstates), L.ptr(ws), L.ptr(e), L.ptr(logp), L.ptr(buf)),
-            "ff_beta_state_partials")
+    L.check(L.lib().ff_beta_state_partials(L.stream(), e.numel(), int(nstates), L.ptr(ws), L.ptr(e), L.ptr(logp), L.ptr(buf)), "ff_beta_state_partials")
 
 
 def beta_finish(buf, shift_dev, logits, beta, n_global):
@@ -528,7 +503,7 @@ def beta_finish(buf, shift_dev, logits, beta, n_global):
     ns = logits.numel()
     f = dict(dtype=torch.float64, device=buf.device)
     est, gphi, mean_e, lpa = torch.empty(8, **f), torch.empty(ns, **f), torch.empty(ns, **f), torch.empty(ns, **f)
-    L.check(L.lib().ff_beta_finish(L.stream(), L.ptr(buf), L.ptr(shift_dev), L.ptr(logits), ns, L.f64(beta), L.i64(n_global),
+    L.check(L.lib().ff_beta_finish(L.stream(), L.ptr(buf), L.ptr(shift_dev), L.ptr(logits), ns, beta, int(n_global),
                                    L.ptr(est), L.ptr(gphi), L.ptr(mean_e), L.ptr(lpa)), "ff_beta_finish")
     return est, gphi, mean_e, lpa
 
@@ -540,7 +515,7 @@ def logprob3d(tab_up, tab_dn, nup, ndn, x, walker_state=None, derivs=False):
     logp = torch.empty(B, dtype=torch.float64, device=x.device)
     grad = torch.empty_like(x) if derivs else None
     lap = torch.empty(B, dtype=torch.float64, device=x.device) if derivs else None
-    L.check(L.lib().ff_logprob3d(L.stream(), L.i64(B), nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
+    L.check(L.lib().ff_logprob3d(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
                                  L.ptr(x), L.ptr(logp), L.ptr(grad), L.ptr(lap)), "ff_logprob3d")
     return (logp, grad, lap) if derivs else logp
 
@@ -551,9 +526,8 @@ def mcmc_sample_noise3d(tab_up, tab_dn, nup, ndn, g0, g, u, tau=0.1, walker_stat
     x = torch.empty_like(g0)
     logp = torch.empty(B, dtype=torch.float64, device=g0.device)
     acc = torch.empty(steps, B, dtype=torch.uint8, device=g0.device)
-    L.check(L.lib().ff_mcmc_sample_noise3d(L.stream(), L.i64(B), nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
-                                           int(steps), L.f64(tau), L.ptr(g0), L.ptr(g), L.ptr(u), L.ptr(x), L.ptr(logp), L.ptr(acc)),
-            "ff_mcmc_sample_noise3d")
+    L.check(L.lib().ff_mcmc_sample_noise3d(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), int(steps), tau, L.ptr(g0),
+                                           L.ptr(g), L.ptr(u), L.ptr(x), L.ptr(logp), L.ptr(acc)), "ff_mcmc_sample_noise3d")
     return x, logp, acc
 
 
@@ -562,9 +536,8 @@ def mcmc_sample3d(tab_up, tab_dn, nup, ndn, B, steps, tau, seed, device, walker_
     x = torch.empty(B, n, 3, dtype=torch.float64, device=device)
     logp = torch.empty(B, dtype=torch.float64, device=device)
     cnt = torch.empty(B, dtype=torch.int32, device=device)
-    L.check(L.lib().ff_mcmc_sample3d(L.stream(), L.i64(B), nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)),
-                                     int(steps), L.f64(tau), C.c_uint64(int(seed) & (2**64 - 1)), L.i64(walker_offset),
-                                     L.ptr(x), L.ptr(logp), L.ptr(cnt)), "ff_mcmc_sample3d")
+    L.check(L.lib().ff_mcmc_sample3d(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), int(steps), tau,
+                                     int(seed) & (2**64 - 1), int(walker_offset), L.ptr(x), L.ptr(logp), L.ptr(cnt)), "ff_mcmc_sample3d")
     return x, logp, cnt
 
 
@@ -574,5 +547,5 @@ def backflow_v_div_f32(net, x):
     B, n, d = x.shape
     v = torch.empty_like(x)
     div = torch.empty(B, dtype=torch.float64, device=x.device)
-    L.check(L.lib().ff_backflow_v_div_f32(L.stream(), L.i64(B), n, d, net.ref(), L.ptr(x), L.ptr(v), L.ptr(div)), "ff_backflow_v_div_f32")
+    L.check(L.lib().ff_backflow_v_div_f32(L.stream(), B, n, d, net.ref(), L.ptr(x), L.ptr(v), L.ptr(div)), "ff_backflow_v_div_f32")
     return v, div

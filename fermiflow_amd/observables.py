@@ -65,7 +65,7 @@ class Observables:
         lib = _lib.lib()
         if self._B is None and lib.ff_observe_buffer_bytes(self.nbins) != 8 * self._words:
             raise RuntimeError("Observables: the library lays the accumulator out differently (include/fermiflow.h)")
-        _lib.check(lib.ff_observe_accumulate(_lib.stream(), _lib.i64(B), self.nup, self.ndown, self.dim, _lib.ptr(x), _lib.f64(self.rmax),
+        _lib.check(lib.ff_observe_accumulate(_lib.stream(), B, self.nup, self.ndown, self.dim, _lib.ptr(x), self.rmax,
                                              self.nbins, _lib.ptr(self._buf)), "ff_observe_accumulate")
         if B > 0:
             self._B = B                        # (only a call that counted fixes the block size)

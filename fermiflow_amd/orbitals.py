@@ -122,12 +122,12 @@ class Orbitals(object):
         if nup < 0 or ndown < 0 or nup + ndown == 0:
             raise ValueError("fermion_states: need nup, ndown >= 0 and at least one particle")
         E = np.ascontiguousarray(self.Es, dtype=np.float64)
-        args = (len(E), E.ctypes.data_as(C.c_void_p), int(nup), int(ndown), C.c_double(float(deltaE)))
-        ns = L.lib().ff_fermion_states(*args, C.c_int64(0), None, None, None)
+        args = (len(E), E.ctypes.data_as(C.c_void_p), int(nup), int(ndown), float(deltaE))
+        ns = L.lib().ff_fermion_states(*args, 0, None, None, None)
         if ns < 0:
             raise ValueError("fermion_states: " + L.lib().ff_last_error().decode())
         up = np.empty((ns, nup), dtype=np.int32); dn = np.empty((ns, ndown), dtype=np.int32); Es = np.empty(ns)
-        L.lib().ff_fermion_states(*args, C.c_int64(ns), up.ctypes.data_as(C.c_void_p), dn.ctypes.data_as(C.c_void_p),
+        L.lib().ff_fermion_states(*args, ns, up.ctypes.data_as(C.c_void_p), dn.ctypes.data_as(C.c_void_p),
                                   Es.ctypes.data_as(C.c_void_p))
         states = tuple((tuple(self.orbitals[i] for i in u), tuple(self.orbitals[i] for i in d)) for u, d in zip(up.tolist(), dn.tolist()))
         ints = all(float(e).is_integer() for e in self.Es)

@@ -41,7 +41,7 @@ def sim_frames(S, z, net, nframes, t0=T0, t1=T1, rtol=1e-6, atol=1e-8, order=Non
         frames = np.full((max(nframes, 1), B, n, d), np.nan)
     stats = np.zeros(4, dtype=np.int32)
     ode = S._ode(t0, t1, rtol, atol, None, order)
-    st = S.lib().ff_cnf_generate_frames(None, C.c_int64(B), n, d, C.byref(net.c), C.byref(ode), S._p(z), int(nframes), S._p(frames), S._p(stats))
+    st = S.lib().ff_cnf_generate_frames(None, B, n, d, C.byref(net.c), C.byref(ode), S._p(z), int(nframes), S._p(frames), S._p(stats))
     if check:
         assert st == 0, S.lib().ff_last_error()
     return st, frames, stats

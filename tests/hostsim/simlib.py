@@ -7,27 +7,10 @@ import os
 import subprocess
 import numpy as np
 
+from fermiflow_amd._abi import FFKernelPlanInfo, FFNet, bind, ode_struct
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
-
-
-class FFNet(C.Structure):
-    _fields_ = [("He", C.c_int32), ("ew1", C.c_void_p), ("eb1", C.c_void_p), ("ew2", C.c_void_p),
-                ("Hm", C.c_int32), ("mw1", C.c_void_p), ("mb1", C.c_void_p), ("mw2", C.c_void_p),
-                ("radial_table", C.c_void_p)]
-
-
-class FFOde(C.Structure):
-    _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("rtol", C.c_double), ("atol", C.c_double),
-                ("max_steps", C.c_int32), ("walker_cost", C.c_void_p), ("walker_order", C.c_void_p),
-                ("walker_h_init", C.c_void_p), ("walker_h_scale", C.c_double), ("walker_h_out", C.c_void_p),
-                ("walker_class", C.c_void_p), ("sens_tol", C.c_double), ("walker_h_scale_loose", C.c_double), ("sens_tol_class", C.c_int32),
-                ("walker_h_uniform", C.c_int32), ("heavy_class", C.c_int32), ("heavy_tol", C.c_double), ("sum_weight", C.c_double),
-                ("compact_finish", C.c_int32), ("after_main_event", C.c_void_p), ("walker_h_equal", C.c_int32)]
-
-
-class FFKernelPlanInfo(C.Structure):
-    _fields_ = [("family", C.c_int32), ("group", C.c_int32), ("round", C.c_int64)]
 
 
 def build():
@@ -44,17 +27,14 @@ def lib():
         alt = os.environ.get("FF_HOSTSIM_LIB")     # e.g. a build of the same sources under the address / UB sanitizers
         if not alt:
             build()
-        _LIB = C.CDLL(alt or os.path.join(HERE, "libff_hostsim.so"))
-        _LIB.ff_last_error.restype = C.c_char_p
-        _LIB.ff_eloc_workspace_bytes.restype = C.c_size_t
-        _LIB.ff_cnf_adjoint_workspace_bytes.restype = C.c_size_t
+        _LIB = bind(C.CDLL(alt or os.path.join(HERE, "libff_hostsim.so")))
     return _LIB
 
 
 def kernel_plan(call, n, d, cus):
     """ff_kernel_plan of the simulator's build: (FF_FAMILY_* id, walkers per group, walkers per round) of call id FF_CALL_*"""
     out = FFKernelPlanInfo()
-    _ck(lib().ff_kernel_plan(call, n, d, C.c_int64(cus), C.byref(out)))
+    _ck(lib().ff_kernel_plan(call, n, d, cus, C.byref(out)))
     return out.family, out.group, out.round
 
 
@@ -84,7 +64,6 @@ class Net:
                        _p(self.m[0]) if self.m else None, _p(self.m[1]) if self.m else None,
                        _p(self.m[2]) if self.m else None, None)
         if table:
-            lib().ff_radial_table_bytes.restype = C.c_size_t
             self.tab = np.zeros(lib().ff_radial_table_bytes() // 8)
             _ck(lib().ff_radial_table_build(None, C.byref(self.c), _p(self.tab)))
             self.c.radial_table = self.tab.ctypes.data
@@ -104,7 +83,7 @@ def logprob(x, nup, ndn, tab_up=None, tab_dn=None, wstate=None, derivs=True):
     x = _d(x); B = x.shape[0]
     tu, td = _tabs(nup, ndn, tab_up, tab_dn); ws = _i(wstate) if wstate is not None else None
     lp = np.empty(B); g = np.empty_like(x) if derivs else None; l = np.empty(B) if derivs else None
-    _ck(lib().ff_logprob(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), _p(ws), _p(x), _p(lp), _p(g), _p(l)))
+    _ck(lib().ff_logprob(None, B, nup, ndn, _p(tu), _p(td), _p(ws), _p(x), _p(lp), _p(g), _p(l)))
     return (lp, g, l) if derivs else lp
 
 
@@ -112,11 +91,11 @@ def slater(x, orb, wstate=None, gout=None):
     x = _d(x); B, n, _ = x.shape
     t = _i(orb); ws = _i(wstate) if wstate is not None else None
     lad = np.empty(B)
-    _ck(lib().ff_slater_logabsdet_fwd(None, C.c_int64(B), n, _p(t), _p(ws), _p(x), _p(lad)))
+    _ck(lib().ff_slater_logabsdet_fwd(None, B, n, _p(t), _p(ws), _p(x), _p(lad)))
     gx = None
     if gout is not None:
         gx = np.empty_like(x); go = _d(gout)
-        _ck(lib().ff_slater_logabsdet_bwd(None, C.c_int64(B), n, _p(t), _p(ws), _p(x), _p(go), _p(gx)))
+        _ck(lib().ff_slater_logabsdet_bwd(None, B, n, _p(t), _p(ws), _p(x), _p(go), _p(gx)))
     return lad, gx
 
 
@@ -125,8 +104,7 @@ def mcmc_noise(g0, g, u, nup, ndn, tau=0.1, tab_up=None, tab_dn=None, wstate=Non
     B = g0.shape[0]; steps = g.shape[0]
     tu, td = _tabs(nup, ndn, tab_up, tab_dn); ws = _i(wstate) if wstate is not None else None
     x = np.empty_like(g0); lp = np.empty(B); acc = np.empty((steps, B), dtype=np.uint8)
-    _ck(lib().ff_mcmc_sample_noise(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), _p(ws), steps, C.c_double(tau),
-                                   _p(g0), _p(g), _p(u), _p(x), _p(lp), _p(acc)))
+    _ck(lib().ff_mcmc_sample_noise(None, B, nup, ndn, _p(tu), _p(td), _p(ws), steps, tau, _p(g0), _p(g), _p(u), _p(x), _p(lp), _p(acc)))
     return x, lp, acc
 
 
@@ -134,8 +112,7 @@ def mcmc(B, nup, ndn, steps, seed, offset=0, tau=0.1):
     n = nup + ndn
     tu, td = _tabs(nup, ndn, None, None)
     x = np.empty((B, n, 2)); lp = np.empty(B); cnt = np.empty(B, dtype=np.int32)
-    _ck(lib().ff_mcmc_sample(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), None, steps, C.c_double(tau),
-                             C.c_uint64(seed), C.c_int64(offset), _p(x), _p(lp), _p(cnt)))
+    _ck(lib().ff_mcmc_sample(None, B, nup, ndn, _p(tu), _p(td), None, steps, tau, seed, offset, _p(x), _p(lp), _p(cnt)))
     return x, lp, cnt
 
 
@@ -143,36 +120,35 @@ def mcmc_continue(x_init, nup, ndn, steps, seed, offset=0, tau=0.1):
     x0 = _d(x_init); B = x0.shape[0]
     tu, td = _tabs(nup, ndn, None, None)
     x = np.empty_like(x0); lp = np.empty(B); cnt = np.empty(B, dtype=np.int32)
-    _ck(lib().ff_mcmc_continue(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), None, steps, C.c_double(tau),
-                               C.c_uint64(seed), C.c_int64(offset), _p(x0), _p(x), _p(lp), _p(cnt)))
+    _ck(lib().ff_mcmc_continue(None, B, nup, ndn, _p(tu), _p(td), None, steps, tau, seed, offset, _p(x0), _p(x), _p(lp), _p(cnt)))
     return x, lp, cnt
 
 
 def rng_fill(B, n, steps, seed, offset=0, dim=2):
     g0 = np.empty((B, n, dim)); g = np.empty((steps, B, n, dim)); u = np.empty((steps, B))
     fn = lib().ff_rng_fill if dim == 2 else lib().ff_rng_fill3d
-    _ck(fn(None, C.c_int64(B), n, steps, C.c_uint64(seed), C.c_int64(offset), _p(g0), _p(g), _p(u)))
+    _ck(fn(None, B, n, steps, seed, offset, _p(g0), _p(g), _p(u)))
     return g0, g, u
 
 
 def backflow(x, net):
     x = _d(x); B, n, d = x.shape
     v = np.empty_like(x); div = np.empty(B)
-    _ck(lib().ff_backflow_v_div(None, C.c_int64(B), n, d, C.byref(net.c), _p(x), _p(v), _p(div)))
+    _ck(lib().ff_backflow_v_div(None, B, n, d, C.byref(net.c), _p(x), _p(v), _p(div)))
     return v, div
 
 
 def potential(x, Z, use_ho=True):
     x = _d(x); B, n, d = x.shape
     V = np.empty(B)
-    _ck(lib().ff_potential(None, C.c_int64(B), n, d, C.c_double(Z), int(use_ho), _p(x), _p(V)))
+    _ck(lib().ff_potential(None, B, n, d, Z, int(use_ho), _p(x), _p(V)))
     return V
 
 
 def mlp(r, w1, b1, w2):
     r = _d(r).reshape(-1); w1, b1, w2 = _d(w1).reshape(-1), _d(b1), _d(w2).reshape(-1)
     v = np.empty_like(r); dv = np.empty_like(r)
-    _ck(lib().ff_mlp_eval(None, C.c_int64(len(r)), len(b1), _p(w1), _p(b1), _p(w2), _p(r), _p(v), _p(dv)))
+    _ck(lib().ff_mlp_eval(None, len(r), len(b1), _p(w1), _p(b1), _p(w2), _p(r), _p(v), _p(dv)))
     return v, dv
 
 
@@ -188,22 +164,22 @@ def warm(h_init=None, h_scale=1.0, h_out=None, uniform=False, max_steps=0, wclas
 
 def _ode(t0, t1, rtol, atol, steps=None, order=None, compact=False):
     q = lambda a: a.ctypes.data if a is not None else None
-    qi = q
-    return FFOde(t0, t1, rtol, atol, int(_WARM.get("max_steps", 0)), q(steps), q(order), q(_WARM.get("h_init")), float(_WARM.get("h_scale", 1.0)),
-                 q(_WARM.get("h_out")), qi(_WARM.get("wclass")), float(_WARM.get("sens_tol", 1.0)), float(_WARM.get("h_scale_loose", 0.0)),
-                 int(_WARM.get("sens_class", 0)), int(bool(_WARM.get("uniform", False))), int(_WARM.get("heavy_class", 0)),
-                 float(_WARM.get("heavy_tol", 0.0)), float(_WARM.get("sum_weight", 0.0)), int(bool(compact)), None, int(bool(_WARM.get("h_equal", False))))
+    W = _WARM.get
+    return ode_struct(t0=t0, t1=t1, rtol=rtol, atol=atol, max_steps=int(W("max_steps", 0)), walker_cost=q(steps), walker_order=q(order),
+                      walker_h_init=q(W("h_init")), walker_h_scale=W("h_scale", 1.0), walker_h_out=q(W("h_out")), walker_class=q(W("wclass")),
+                      sens_tol=W("sens_tol", 1.0), walker_h_scale_loose=W("h_scale_loose", 0.0), sens_tol_class=int(W("sens_class", 0)),
+                      walker_h_uniform=bool(W("uniform", False)), heavy_class=int(W("heavy_class", 0)), heavy_tol=W("heavy_tol", 0.0),
+                      sum_weight=W("sum_weight", 0.0), compact_finish=bool(compact), after_main_event=None, walker_h_equal=bool(W("h_equal", False)))
 
 
 def walker_order(cost, hval=None):
     cost = _i(cost); order = np.empty_like(cost)
-    lib().ff_walker_order_workspace_bytes.restype = C.c_size_t
-    ws = np.zeros((lib().ff_walker_order_workspace_bytes(C.c_int64(len(cost))) + 7) // 8)
+    ws = np.zeros((lib().ff_walker_order_workspace_bytes(len(cost)) + 7) // 8)
     if hval is None:
-        _ck(lib().ff_walker_order(None, C.c_int64(len(cost)), _p(cost), _p(order), _p(ws)))
+        _ck(lib().ff_walker_order(None, len(cost), _p(cost), _p(order), _p(ws)))
         return order
     hval = _d(hval); hm = np.empty(1)
-    _ck(lib().ff_walker_order_mean(None, C.c_int64(len(cost)), _p(cost), _p(order), _p(ws), _p(hval), _p(hm)))
+    _ck(lib().ff_walker_order_mean(None, len(cost), _p(cost), _p(order), _p(ws), _p(hval), _p(hm)))
     return order, hm[0]
 
 
@@ -211,11 +187,10 @@ def walker_schedule(cost, hval, scale_in, prev=None, interval=0.0, counts=None, 
     """ff_walker_schedule -> (order, mean(hval), hs, updated scale table)"""
     cost = _i(cost); hval = _d(hval); scale_in = _d(scale_in)
     order = np.empty_like(cost); hm = np.empty(1); hs = np.empty_like(hval); scale_out = np.full(32, np.nan)
-    lib().ff_walker_order_workspace_bytes.restype = C.c_size_t
-    ws = np.zeros((lib().ff_walker_order_workspace_bytes(C.c_int64(len(cost))) + 7) // 8)
+    ws = np.zeros((lib().ff_walker_order_workspace_bytes(len(cost)) + 7) // 8)
     pc, ph, pe = (None, None, None) if prev is None else (_i(prev[0]), _d(prev[1]), _d(prev[2]))
-    _ck(lib().ff_walker_schedule(None, C.c_int64(len(cost)), _p(cost), _p(order), _p(ws), _p(hval), _p(hm), _p(scale_in), _p(scale_out),
-                                 _p(pc), _p(ph), _p(pe), _p(_d(counts)) if counts is not None else None, C.c_double(interval), _p(hs), C.c_double(shrink_at)))
+    _ck(lib().ff_walker_schedule(None, len(cost), _p(cost), _p(order), _p(ws), _p(hval), _p(hm), _p(scale_in), _p(scale_out),
+                                 _p(pc), _p(ph), _p(pe), _p(_d(counts)) if counts is not None else None, interval, _p(hs), shrink_at))
     return order, hm[0], hs, scale_out
 
 
@@ -224,36 +199,34 @@ def adam_step(params, grads, m, v, lr, beta1, beta2, eps, wd, step):
     n = len(params)
     arr = lambda xs: (C.c_void_p * n)(*[x.ctypes.data for x in xs])
     sizes = (C.c_int64 * n)(*[x.size for x in params])
-    _ck(lib().ff_adam_step(None, n, sizes, arr(params), arr(grads), arr(m), arr(v), C.c_double(lr), C.c_double(beta1), C.c_double(beta2),
-                           C.c_double(eps), C.c_double(wd), C.c_int64(step)))
+    _ck(lib().ff_adam_step(None, n, sizes, arr(params), arr(grads), arr(m), arr(v), lr, beta1, beta2, eps, wd, step))
 
 
 def scale_counts(cost, hs, he, interval=0.0):
     cost = _i(cost); counts = np.zeros(128)
-    _ck(lib().ff_scale_counts(None, C.c_int64(len(cost)), _p(cost), _p(_d(hs)), _p(_d(he)), C.c_double(interval), _p(counts)))
+    _ck(lib().ff_scale_counts(None, len(cost), _p(cost), _p(_d(hs)), _p(_d(he)), interval, _p(counts)))
     return counts
 
 
 def cnf_generate(z, net, t0=0.0, t1=1.0, rtol=1e-6, atol=1e-8, steps=None, order=None):
     z = _d(z); B, n, d = z.shape
     x = np.empty_like(z); stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol, steps, order)
-    _ck(lib().ff_cnf_generate(None, C.c_int64(B), n, d, C.byref(net.c), C.byref(ode), _p(z), _p(x), _p(stats)))
+    _ck(lib().ff_cnf_generate(None, B, n, d, C.byref(net.c), C.byref(ode), _p(z), _p(x), _p(stats)))
     return x, stats
 
 
 def cnf_delta_logp(x, net, t0=0.0, t1=1.0, rtol=1e-6, atol=1e-8, steps=None, order=None):
     x = _d(x); B, n, d = x.shape
     z = np.empty_like(x); dl = np.empty(B); stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol, steps, order)
-    _ck(lib().ff_cnf_delta_logp(None, C.c_int64(B), n, d, C.byref(net.c), C.byref(ode), _p(x), _p(z), _p(dl), _p(stats)))
+    _ck(lib().ff_cnf_delta_logp(None, B, n, d, C.byref(net.c), C.byref(ode), _p(x), _p(z), _p(dl), _p(stats)))
     return z, dl, stats
 
 
 def cnf_adjoint(z0, a_z, a_d, net, t0=0.0, t1=1.0, rtol=1e-6, atol=1e-8, steps=None, order=None):
     z0, a_z, a_d = _d(z0), _d(a_z), _d(a_d); B, n, d = z0.shape
     gx = np.empty_like(z0); gp = np.empty(net.nparams); stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol, steps, order)
-    ws = np.zeros(max(1, lib().ff_cnf_adjoint_workspace_bytes(C.c_int64(B), n, d, net.c.He, net.c.Hm) // 8))
-    _ck(lib().ff_cnf_adjoint(None, C.c_int64(B), n, d, C.byref(net.c), C.byref(ode), _p(z0), _p(a_z), _p(a_d),
-                             _p(gx), _p(gp), _p(ws), _p(stats)))
+    ws = np.zeros(max(1, lib().ff_cnf_adjoint_workspace_bytes(B, n, d, net.c.He, net.c.Hm) // 8))
+    _ck(lib().ff_cnf_adjoint(None, B, n, d, C.byref(net.c), C.byref(ode), _p(z0), _p(a_z), _p(a_d), _p(gx), _p(gp), _p(ws), _p(stats)))
     return gx, gp, stats
 
 
@@ -264,10 +237,9 @@ def eloc(x, nup, ndn, net, Z, use_ho=True, t0=0.0, t1=1.0, rtol=1e-6, atol=1e-8,
     o = dict(logp=np.empty(B), grad=np.empty_like(x), lap=np.empty(B), V=np.empty(B), eloc=np.empty(B),
              z=np.empty_like(x), dlogp=np.empty(B), glogp0=np.empty_like(x))
     stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol, steps, order)
-    wk = np.zeros(lib().ff_eloc_workspace_bytes(C.c_int64(B), n, 2) // 8)
-    _ck(lib().ff_eloc(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), _p(ws), C.byref(net.c), C.byref(ode), C.c_double(Z),
-                      int(use_ho), _p(x), _p(o["logp"]), _p(o["grad"]), _p(o["lap"]), _p(o["V"]), _p(o["eloc"]),
-                      _p(o["z"]), _p(o["dlogp"]), _p(o["glogp0"]), _p(wk), _p(stats)))
+    wk = np.zeros(lib().ff_eloc_workspace_bytes(B, n, 2) // 8)
+    _ck(lib().ff_eloc(None, B, nup, ndn, _p(tu), _p(td), _p(ws), C.byref(net.c), C.byref(ode), Z, int(use_ho), _p(x), _p(o["logp"]), _p(o["grad"]),
+                      _p(o["lap"]), _p(o["V"]), _p(o["eloc"]), _p(o["z"]), _p(o["dlogp"]), _p(o["glogp0"]), _p(wk), _p(stats)))
     o["stats"] = stats
     return o
 
@@ -278,12 +250,10 @@ def eloc_nd(x, nup, ndn, net, Z, use_ho=True, t0=0.0, t1=1.0, rtol=1e-6, atol=1e
     tu, td = _tabs(nup, ndn, tab_up, tab_dn); ws = _i(wstate) if wstate is not None else None
     o = dict(logp=np.empty(B), grad=np.empty_like(x), lap=np.empty(B), V=np.empty(B), eloc=np.empty(B), glogp0=np.empty_like(x))
     stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol, compact=compact)
-    lib().ff_eloc_nd_workspace_bytes.restype = C.c_size_t
-    nb = lib().ff_eloc_nd_workspace_bytes(C.c_int64(B), n, d, int(bool(compact)))
+    nb = lib().ff_eloc_nd_workspace_bytes(B, n, d, int(bool(compact)))
     wk = np.zeros(nb // 8)
-    _ck(lib().ff_eloc_nd(None, C.c_int64(B), nup, ndn, d, _p(tu), _p(td), _p(ws), C.byref(net.c), C.byref(ode), C.c_double(Z),
-                         int(use_ho), _p(x), _p(o["logp"]), _p(o["grad"]), _p(o["lap"]), _p(o["V"]), _p(o["eloc"]),
-                         None, None, _p(o["glogp0"]), _p(wk), _p(stats)))
+    _ck(lib().ff_eloc_nd(None, B, nup, ndn, d, _p(tu), _p(td), _p(ws), C.byref(net.c), C.byref(ode), Z, int(use_ho), _p(x), _p(o["logp"]), _p(o["grad"]),
+                         _p(o["lap"]), _p(o["V"]), _p(o["eloc"]), None, None, _p(o["glogp0"]), _p(wk), _p(stats)))
     M = n * d
     o["z"] = wk[:B * M].reshape(B, n, d).copy()
     dl0 = B * M if (compact and M > 24) else B * (M * M + 4 * M)
@@ -293,24 +263,23 @@ def eloc_nd(x, nup, ndn, net, Z, use_ho=True, t0=0.0, t1=1.0, rtol=1e-6, atol=1e
 
 def reduce_energy(e, logp, shift):
     e = _d(e); logp = _d(logp); sh = np.array([shift], dtype=np.float64); out = np.empty(4)
-    _ck(lib().ff_reduce_energy(None, C.c_int64(len(e)), _p(e), _p(logp), _p(sh), _p(out)))
+    _ck(lib().ff_reduce_energy(None, len(e), _p(e), _p(logp), _p(sh), _p(out)))
     return out
 
 
 def energy_estimate(e, logp, shift, n_global, ws=None):
     """ff_energy_estimate: (sums4, est3 or None, workspace) -- pass the returned workspace to the next call (zeroed once)."""
     e = _d(e); logp = _d(logp); sh = np.array([shift], dtype=np.float64)
-    lib().ff_energy_estimate_workspace_bytes.restype = C.c_size_t
     if ws is None:
-        ws = np.zeros(lib().ff_energy_estimate_workspace_bytes(C.c_int64(len(e))) // 8)
+        ws = np.zeros(lib().ff_energy_estimate_workspace_bytes(len(e)) // 8)
     sums = np.empty(4); est = np.empty(3) if n_global else None
-    _ck(lib().ff_energy_estimate(None, C.c_int64(len(e)), _p(e), _p(logp), _p(sh), C.c_int64(n_global), _p(sums), _p(est), _p(ws)))
+    _ck(lib().ff_energy_estimate(None, len(e), _p(e), _p(logp), _p(sh), n_global, _p(sums), _p(est), _p(ws)))
     return sums, est, ws
 
 
 def energy_finish(sums4, shift, n):
     sums4 = _d(sums4); sh = np.array([shift], dtype=np.float64); out = np.empty(3)
-    _ck(lib().ff_energy_finish(None, _p(sums4), _p(sh), C.c_int64(n), _p(out)))
+    _ck(lib().ff_energy_finish(None, _p(sums4), _p(sh), n, _p(out)))
     return out
 
 
@@ -319,38 +288,35 @@ def cnf_adjoint_energy(z0, glogp0, eloc, e_mean, scale, net, t0=0.0, t1=1.0, rto
     em = np.atleast_1d(np.asarray(e_mean, dtype=np.float64)).copy()
     mi = _i(mean_index) if mean_index is not None else None
     gx = np.empty_like(z0); gp = np.empty(3 * net.c.He + 3 * net.c.Hm); stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol)
-    lib().ff_cnf_adjoint_workspace_bytes.restype = C.c_size_t
-    ws = np.zeros(max(1, lib().ff_cnf_adjoint_workspace_bytes(C.c_int64(B), n, d, net.c.He, net.c.Hm) // 8))
-    _ck(lib().ff_cnf_adjoint_energy(None, C.c_int64(B), n, d, C.byref(net.c), C.byref(ode), _p(z0), _p(glogp0), _p(eloc), _p(em),
-                                    _p(mi), C.c_double(scale), _p(gx), _p(gp), _p(ws), _p(stats)))
+    ws = np.zeros(max(1, lib().ff_cnf_adjoint_workspace_bytes(B, n, d, net.c.He, net.c.Hm) // 8))
+    _ck(lib().ff_cnf_adjoint_energy(None, B, n, d, C.byref(net.c), C.byref(ode), _p(z0), _p(glogp0), _p(eloc), _p(em),
+                                    _p(mi), scale, _p(gx), _p(gp), _p(ws), _p(stats)))
     return gx, gp, stats
 
 
 def beta_estimator(e, logp, ws, logits, beta, shift, n_global=None):
     """ff_reduce_moments + ff_beta_state_partials + ff_beta_finish on one rank: (est8, gphi, mean_e, logp_all)."""
     e = _d(e); logp = _d(logp); ws = _i(ws); logits = _d(logits); ns = len(logits)
-    lib().ff_beta_buffer_doubles.restype = C.c_size_t
     buf = np.zeros(lib().ff_beta_buffer_doubles(ns))
     sh = np.array([shift], dtype=np.float64)
     mom = np.empty(2)
-    _ck(lib().ff_reduce_moments(None, C.c_int64(len(e)), _p(e), C.c_double(0.0), _p(sh), C.c_double(1.0), _p(mom)))
-    _ck(lib().ff_beta_state_partials(None, C.c_int64(len(e)), ns, _p(ws), _p(e), _p(logp), _p(buf)))
+    _ck(lib().ff_reduce_moments(None, len(e), _p(e), 0.0, _p(sh), 1.0, _p(mom)))
+    _ck(lib().ff_beta_state_partials(None, len(e), ns, _p(ws), _p(e), _p(logp), _p(buf)))
     buf[:2] = mom
     est, gphi, mean_e, lpa = np.empty(8), np.empty(ns), np.empty(ns), np.empty(ns)
-    _ck(lib().ff_beta_finish(None, _p(buf), _p(sh), _p(logits), ns, C.c_double(beta), C.c_int64(n_global or len(e)), _p(est), _p(gphi),
-                             _p(mean_e), _p(lpa)))
+    _ck(lib().ff_beta_finish(None, _p(buf), _p(sh), _p(logits), ns, beta, n_global or len(e), _p(est), _p(gphi), _p(mean_e), _p(lpa)))
     return est, gphi, mean_e, lpa
 
 
 def moments(e, shift=0.0):
     e = _d(e); out = np.empty(2)
-    _ck(lib().ff_reduce_moments(None, C.c_int64(len(e)), _p(e), C.c_double(shift), None, C.c_double(1.0), _p(out)))
+    _ck(lib().ff_reduce_moments(None, len(e), _p(e), shift, None, 1.0, _p(out)))
     return out
 
 
 def state_sums(e, ws, nstates):
     e = _d(e); ws = _i(ws); sums = np.empty(nstates); cnt = np.empty(nstates)
-    _ck(lib().ff_state_sums(None, C.c_int64(len(e)), int(nstates), _p(ws), _p(e), _p(sums), _p(cnt)))
+    _ck(lib().ff_state_sums(None, len(e), int(nstates), _p(ws), _p(e), _p(sums), _p(cnt)))
     return sums, cnt
 
 
@@ -359,7 +325,7 @@ def logprob3d(x, nup, ndn, tab_up=None, tab_dn=None, wstate=None):
     x = _d(x); B = x.shape[0]
     tu, td = _tabs(nup, ndn, tab_up, tab_dn); ws = _i(wstate) if wstate is not None else None
     lp = np.empty(B); g = np.empty_like(x); lap = np.empty(B)
-    _ck(lib().ff_logprob3d(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), _p(ws), _p(x), _p(lp), _p(g), _p(lap)))
+    _ck(lib().ff_logprob3d(None, B, nup, ndn, _p(tu), _p(td), _p(ws), _p(x), _p(lp), _p(g), _p(lap)))
     return lp, g, lap
 
 
@@ -367,7 +333,7 @@ def mcmc_noise3d(g0, g, u, nup, ndn, tau=0.1, tab_up=None, tab_dn=None, wstate=N
     g0, g, u = _d(g0), _d(g), _d(u); B, steps = g0.shape[0], g.shape[0]
     tu, td = _tabs(nup, ndn, tab_up, tab_dn); ws = _i(wstate) if wstate is not None else None
     x = np.empty_like(g0); lp = np.empty(B); acc = np.empty((steps, B), dtype=np.uint8)
-    _ck(lib().ff_mcmc_sample_noise3d(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), _p(ws), steps, C.c_double(tau), _p(g0), _p(g), _p(u),
+    _ck(lib().ff_mcmc_sample_noise3d(None, B, nup, ndn, _p(tu), _p(td), _p(ws), steps, tau, _p(g0), _p(g), _p(u),
                                      _p(x), _p(lp), acc.ctypes.data_as(C.c_void_p)))
     return x, lp, acc
 
@@ -375,15 +341,14 @@ def mcmc_noise3d(g0, g, u, nup, ndn, tau=0.1, tab_up=None, tab_dn=None, wstate=N
 def mcmc3d(B, nup, ndn, steps, seed, offset=0, tau=0.1, tab_up=None, tab_dn=None):
     tu, td = _tabs(nup, ndn, tab_up, tab_dn)
     x = np.empty((B, nup + ndn, 3)); lp = np.empty(B); cnt = np.empty(B, dtype=np.int32)
-    _ck(lib().ff_mcmc_sample3d(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), None, steps, C.c_double(tau), C.c_uint64(seed),
-                               C.c_int64(offset), _p(x), _p(lp), _p(cnt)))
+    _ck(lib().ff_mcmc_sample3d(None, B, nup, ndn, _p(tu), _p(td), None, steps, tau, seed, offset, _p(x), _p(lp), _p(cnt)))
     return x, lp, cnt
 
 
 def backflow_f32(x, net):
     x = _d(x); B, n, d = x.shape
     v = np.empty_like(x); div = np.empty(B)
-    _ck(lib().ff_backflow_v_div_f32(None, C.c_int64(B), n, d, C.byref(net.c), _p(x), _p(v), _p(div)))
+    _ck(lib().ff_backflow_v_div_f32(None, B, n, d, C.byref(net.c), _p(x), _p(v), _p(div)))
     return v, div
 
 
@@ -394,10 +359,9 @@ def eloc3d(x, nup, ndn, net, Z, use_ho=True, t0=0.0, t1=1.0, rtol=1e-6, atol=1e-
     o = dict(logp=np.empty(B), grad=np.empty_like(x), lap=np.empty(B), V=np.empty(B), eloc=np.empty(B),
              z=np.empty_like(x), dlogp=np.empty(B), glogp0=np.empty_like(x))
     stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol)
-    wk = np.zeros(lib().ff_eloc_workspace_bytes(C.c_int64(B), n, 3) // 8)
-    _ck(lib().ff_eloc_sensitivities(None, C.c_int64(B), n, 3, C.byref(net.c), C.byref(ode), _p(x), _p(wk), _p(stats)))
-    _ck(lib().ff_eloc_finish3d(None, C.c_int64(B), nup, ndn, _p(tu), _p(td), _p(ws), C.c_double(Z), int(use_ho), _p(x), _p(wk),
-                               _p(o["logp"]), _p(o["grad"]), _p(o["lap"]), _p(o["V"]), _p(o["eloc"]), _p(o["z"]), _p(o["dlogp"]),
-                               _p(o["glogp0"])))
+    wk = np.zeros(lib().ff_eloc_workspace_bytes(B, n, 3) // 8)
+    _ck(lib().ff_eloc_sensitivities(None, B, n, 3, C.byref(net.c), C.byref(ode), _p(x), _p(wk), _p(stats)))
+    _ck(lib().ff_eloc_finish3d(None, B, nup, ndn, _p(tu), _p(td), _p(ws), Z, int(use_ho), _p(x), _p(wk), _p(o["logp"]), _p(o["grad"]), _p(o["lap"]),
+                               _p(o["V"]), _p(o["eloc"]), _p(o["z"]), _p(o["dlogp"]), _p(o["glogp0"])))
     o["stats"] = stats
     return o

@@ -66,7 +66,6 @@ def pair_counts(nup, ndn):
 
 # ---- the accumulator as the C ABI lays it out: uint64 words [calls, walkers | sum | sumsq | scratch (S words + ticket)]
 def new_buffer(lib, nbins):
-    lib.ff_observe_buffer_bytes.restype = C.c_size_t
     nb = lib.ff_observe_buffer_bytes(int(nbins))
     assert nb == 8 * (3 + 15 * (nbins + 2))
     return np.zeros(nb // 8, dtype=np.uint64)
@@ -83,5 +82,5 @@ def accumulate(lib, x, nup, ndn, rmax, nbins, acc, B=None, d=None, x_null=False,
     x = np.ascontiguousarray(x, dtype=np.float64)
     B = x.shape[0] if B is None else B
     d = x.shape[2] if d is None else d
-    return lib.ff_observe_accumulate(None, C.c_int64(B), int(nup), int(ndn), int(d), None if x_null else x.ctypes.data_as(C.c_void_p),
-                                     C.c_double(rmax), int(nbins), None if acc_null else acc.ctypes.data_as(C.c_void_p))
+    return lib.ff_observe_accumulate(None, B, int(nup), int(ndn), int(d), None if x_null else x.ctypes.data_as(C.c_void_p),
+                                     rmax, int(nbins), None if acc_null else acc.ctypes.data_as(C.c_void_p))

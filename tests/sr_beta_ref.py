@@ -1,6 +1,5 @@
 """Shared by tests/test_sr_beta_hostsim.py and tests/test_gpu_sr_beta.py: cases, data, ctypes calls into the host simulator's library and
 the long-double references of the per-state moments (ff_sr_state_moments / ff_sr_state_finish)."""
-import ctypes as C
 
 import numpy as np
 
@@ -112,8 +111,7 @@ def check_finished(f, ob, g, fr, scale=1.0):
 
 # ---- host simulator: ctypes calls (S = tests.hostsim.simlib)
 def _ws(lib, B, P, ns):
-    lib.ff_sr_state_moments_workspace_bytes.restype = C.c_size_t
-    return np.full(max(1, lib.ff_sr_state_moments_workspace_bytes(C.c_int64(B), P, ns) // 8), np.nan)
+    return np.full(max(1, lib.ff_sr_state_moments_workspace_bytes(B, P, ns) // 8), np.nan)
 
 
 def sim_state_moments(S, O, e, ws, mean_e, check=True, ns=None):
@@ -125,7 +123,7 @@ def sim_state_moments(S, O, e, ws, mean_e, check=True, ns=None):
     ns = len(mean_e) if ns is None else ns
     work = _ws(lib, B, P, ns)
     sums = np.full(sums_len(max(P, 1), max(ns, 1)), np.nan)
-    st = lib.ff_sr_state_moments(None, C.c_int64(B), P, ns, S._p(O), S._p(e), S._p(ws), S._p(mean_e), S._p(sums), S._p(work))
+    st = lib.ff_sr_state_moments(None, B, P, ns, S._p(O), S._p(e), S._p(ws), S._p(mean_e), S._p(sums), S._p(work))
     if check:
         assert st == 0, lib.ff_last_error()
     return st, sums

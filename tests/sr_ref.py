@@ -59,8 +59,7 @@ def sim_scores(S, z, glogp0, net, tol, order=None, check=True, scores=None, null
         scores = np.full((B, net.nparams), 7.0)
     stats = np.zeros(4, dtype=np.int32)
     ode = S._ode(T0, T1, tol["rtol"], tol["atol"], None, order)
-    st = S.lib().ff_cnf_adjoint_scores(None, C.c_int64(B), n, d, C.byref(net.c), C.byref(ode), S._p(z), S._p(g0),
-                                       None if null_scores else S._p(scores), None, S._p(stats))
+    st = S.lib().ff_cnf_adjoint_scores(None, B, n, d, C.byref(net.c), C.byref(ode), S._p(z), S._p(g0), None if null_scores else S._p(scores), None, S._p(stats))
     if check:
         assert st == 0, S.lib().ff_last_error()
     return st, scores, stats
@@ -80,13 +79,12 @@ def sr_sums_len(P):
 def sim_moments(S, O, e, emean, check=True):
     """ff_sr_moments of the simulator's library: (status, sums)"""
     lib = S.lib()
-    lib.ff_sr_moments_workspace_bytes.restype = C.c_size_t
     O = np.ascontiguousarray(O, dtype=np.float64); e = np.ascontiguousarray(e, dtype=np.float64)
     B, P = O.shape
-    ws = np.full(max(1, lib.ff_sr_moments_workspace_bytes(C.c_int64(B), P) // 8), np.nan)
+    ws = np.full(max(1, lib.ff_sr_moments_workspace_bytes(B, P) // 8), np.nan)
     sums = np.full(sr_sums_len(max(P, 1)), np.nan)
     em = np.array([emean], dtype=np.float64)
-    st = lib.ff_sr_moments(None, C.c_int64(B), P, S._p(O), S._p(e), S._p(em), S._p(sums), S._p(ws))
+    st = lib.ff_sr_moments(None, B, P, S._p(O), S._p(e), S._p(em), S._p(sums), S._p(ws))
     if check:
         assert st == 0, lib.ff_last_error()
     return st, sums

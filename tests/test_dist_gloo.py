@@ -62,25 +62,22 @@ def test_two_rank_ground_state_estimator_matches_single_process():
 
 def _beta_worker(rank, world, port, eloc_all, logp_all, ws_all, logits, beta, shift, out):
     _init(rank, world, port)
-    import ctypes as C
     from fermiflow_amd import dist as D
     from tests.hostsim import simlib as S
     B, ns = len(eloc_all), len(logits)
     off, cnt = D.shard(B)
     e, lp, ws = (np.ascontiguousarray(a[off:off + cnt]) for a in (eloc_all, logp_all, ws_all))
     lib = S.lib()
-    lib.ff_beta_buffer_doubles.restype = C.c_size_t
     buf = np.zeros(lib.ff_beta_buffer_doubles(ns))
     sh = np.array([shift])
     mom = np.empty(2)
-    S._ck(lib.ff_reduce_moments(None, C.c_int64(cnt), S._p(e), C.c_double(0.0), S._p(sh), C.c_double(1.0), S._p(mom)))
-    S._ck(lib.ff_beta_state_partials(None, C.c_int64(cnt), ns, S._p(S._i(ws)), S._p(e), S._p(lp), S._p(buf)))
+    S._ck(lib.ff_reduce_moments(None, cnt, S._p(e), 0.0, S._p(sh), 1.0, S._p(mom)))
+    S._ck(lib.ff_beta_state_partials(None, cnt, ns, S._p(S._i(ws)), S._p(e), S._p(lp), S._p(buf)))
     buf[:2] = mom
     t = torch.from_numpy(buf)
     D.all_reduce_sum_(t)
     est, gphi, mean_e, lpa = np.empty(8), np.empty(ns), np.empty(ns), np.empty(ns)
-    S._ck(lib.ff_beta_finish(None, S._p(buf), S._p(sh), S._p(np.ascontiguousarray(logits)), ns, C.c_double(beta), C.c_int64(B),
-                             S._p(est), S._p(gphi), S._p(mean_e), S._p(lpa)))
+    S._ck(lib.ff_beta_finish(None, S._p(buf), S._p(sh), S._p(np.ascontiguousarray(logits)), ns, beta, B, S._p(est), S._p(gphi), S._p(mean_e), S._p(lpa)))
     out[rank] = (est, gphi, mean_e)
     dist.destroy_process_group()
 

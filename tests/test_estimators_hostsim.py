@@ -2,7 +2,6 @@
 tests/test_gpu_estimators.py (the same cases, tests/estimator_cases.py, at sizes the simulator runs in seconds), so that the references
 and expectations are checked before a GPU sees them.  The simulator's reduction workgroups have 4 threads (hip_shim.h: FF_RBLOCK), so
 its serial chains are longer than the device's; the bounds are the device's all the same."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -28,21 +27,19 @@ class _Sim:
     def reduce_moments(e, shift=0.0, shift_dev=None, scale=1.0):
         e = S._d(e); out = np.empty(2)
         sd = None if shift_dev is None else np.array([shift_dev], dtype=np.float64)
-        S._ck(S.lib().ff_reduce_moments(None, C.c_int64(len(e)), S._p(e), C.c_double(shift), S._p(sd), C.c_double(scale), S._p(out)))
+        S._ck(S.lib().ff_reduce_moments(None, len(e), S._p(e), shift, S._p(sd), scale, S._p(out)))
         return out
 
     @staticmethod
     def beta(e, logp, ws, logits, beta, shift):
         e, logp, ws, logits = S._d(e), S._d(logp), S._i(ws), S._d(logits)
         ns = len(logits)
-        S.lib().ff_beta_buffer_doubles.restype = C.c_size_t
         buf = np.zeros(S.lib().ff_beta_buffer_doubles(ns))
         sh = np.array([shift], dtype=np.float64)
         buf[:2] = _Sim.reduce_moments(e, shift_dev=shift, scale=1.0)
-        S._ck(S.lib().ff_beta_state_partials(None, C.c_int64(len(e)), ns, S._p(ws), S._p(e), S._p(logp), S._p(buf)))
+        S._ck(S.lib().ff_beta_state_partials(None, len(e), ns, S._p(ws), S._p(e), S._p(logp), S._p(buf)))
         est, gphi, mean_e, lpa = np.empty(8), np.empty(ns), np.empty(ns), np.empty(ns)
-        S._ck(S.lib().ff_beta_finish(None, S._p(buf), S._p(sh), S._p(logits), ns, C.c_double(beta), C.c_int64(len(e)), S._p(est), S._p(gphi),
-                                     S._p(mean_e), S._p(lpa)))
+        S._ck(S.lib().ff_beta_finish(None, S._p(buf), S._p(sh), S._p(logits), ns, beta, len(e), S._p(est), S._p(gphi), S._p(mean_e), S._p(lpa)))
         return buf[2:].reshape(ns, R.SS_K, 4).copy(), est, gphi, mean_e, lpa
 
     @staticmethod
@@ -55,7 +52,7 @@ class _Sim:
         if into is None:
             return S.scale_counts(cost, hs, he, interval)
         cost, into = S._i(cost), np.array(into, dtype=np.float64)
-        S._ck(S.lib().ff_scale_counts(None, C.c_int64(len(cost)), S._p(cost), S._p(S._d(hs)), S._p(S._d(he)), C.c_double(interval), S._p(into)))
+        S._ck(S.lib().ff_scale_counts(None, len(cost), S._p(cost), S._p(S._d(hs)), S._p(S._d(he)), interval, S._p(into)))
         return into
 
 

@@ -176,7 +176,7 @@ def test_refusals_and_the_single_frame(golden):
     ode = S._ode(0.0, 1.0, 1e-6, 1e-8)
 
     def call(B, n, d, zp, nframes, fp, netc=net.c, odec=ode):
-        return lib.ff_cnf_generate_frames(None, C.c_int64(B), n, d, C.byref(netc), C.byref(odec), zp, nframes, fp, S._p(stats))
+        return lib.ff_cnf_generate_frames(None, B, n, d, C.byref(netc), C.byref(odec), zp, nframes, fp, S._p(stats))
 
     def refused(st, code):
         assert st == code and lib.ff_last_error().decode().startswith("ff_cnf_generate_frames:"), (st, lib.ff_last_error())

@@ -261,10 +261,10 @@ def test_ff_comm_single_rank_all_reduce():
         for n in (4, 300):
             buf = torch.arange(1, n + 1, dtype=torch.float64, device=dev) / 7
             want = buf.clone()
-            L.check(lib.ff_comm_allreduce(comm, L.stream(), L.ptr(buf), L.i64(n)), "ff_comm_allreduce")
+            L.check(lib.ff_comm_allreduce(comm, L.stream(), L.ptr(buf), n), "ff_comm_allreduce")
             torch.cuda.synchronize()
             assert torch.equal(buf, want)
-        assert lib.ff_comm_allreduce(comm, L.stream(), None, L.i64(3)) != 0            # null buffer: FF_EINVAL, no crash
+        assert lib.ff_comm_allreduce(comm, L.stream(), None, 3) != 0            # null buffer: FF_EINVAL, no crash
     finally:
         L.check(lib.ff_comm_destroy(comm), "ff_comm_destroy")
     assert lib.ff_comm_destroy(None) == 0

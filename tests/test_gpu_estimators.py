@@ -81,7 +81,7 @@ class _Dev:
         if into is None:
             return N(native.scale_counts(ct, ht, et, interval))
         counts = self._t(into)      # the C entry point adds to what the buffer holds
-        L.check(L.lib().ff_scale_counts(L.stream(), L.i64(ct.numel()), L.ptr(ct), L.ptr(ht), L.ptr(et), L.f64(interval), L.ptr(counts)),
+        L.check(L.lib().ff_scale_counts(L.stream(), ct.numel(), L.ptr(ct), L.ptr(ht), L.ptr(et), interval, L.ptr(counts)),
                 "ff_scale_counts")
         return N(counts)
 

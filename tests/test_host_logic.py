@@ -18,6 +18,8 @@ def test_library_exports_every_declared_symbol():
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]
     assert not missing, missing
     assert declared == set(_lib.SYMBOLS)
+    from fermiflow_amd import _abi
+    assert declared == set(_abi.SIGNATURES) and _lib.SYMBOLS == list(_abi.SIGNATURES)
     from fermiflow_amd import _lib as L
     assert lib.ff_version() == L.ABI_VERSION
 
@@ -62,9 +64,71 @@ def test_abi_argument_errors_without_gpu():
     assert lib.ff_reduce_energy(None, C.c_int64(4), p8, None, p8, p8) == 1
     assert lib.ff_energy_finish(None, p8, p8, C.c_int64(0), p8) == 1
     assert lib.ff_stream_delay(None, C.c_double(-1.0)) == 1 and lib.ff_stream_delay(None, C.c_double(1e9)) == 1
-    assert lib.ff_cnf_adjoint_energy(None, C.c_int64(4), 6, 2, C.byref(net), C.byref(ode), p8, p8, None, p8, C.c_double(0.25),
+    assert lib.ff_cnf_adjoint_energy(None, C.c_int64(4), 6, 2, C.byref(net), C.byref(ode), p8, p8, None, p8, None, C.c_double(0.25),
                                      None, p8, p8, None) == 1                       # eloc missing
     assert lib.ff_cnf_adjoint(None, C.c_int64(4), 6, 2, C.byref(net), C.byref(ode), p8, p8, None, None, p8, p8, None) == 1   # a_d missing
+
+
+def test_signature_table_is_the_header():
+    """fermiflow_amd/_abi.py SIGNATURES against include/fermiflow.h, prototype by prototype, through a dictionary of C spellings
+    written out HERE: a parameter type the header starts to use fails by name until it is added on purpose."""
+    import ctypes as C
+    from fermiflow_amd import _abi, _lib
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "fermiflow.h")).read(), flags=re.S)
+    protos = re.findall(r"^(int|int64_t|size_t|const char\*)\s+(ff_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)
+    assert [name for _, name, _ in protos] == re.findall(r"\b(ff_\w+)\s*\(", hdr) and len(protos) == 69      # no prototype the pattern misses
+    data = ("const double*", "double*", "const int32_t*", "int32_t*", "const int64_t*", "uint8_t*", "void*", "const void*",
+            "ff_comm*", "ff_comm**", "double* const*", "const double* const*")
+    ctype = {"int": C.c_int, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "double": C.c_double, "size_t": C.c_size_t,
+             "const char*": C.c_char_p, "const ff_net*": C.POINTER(_abi.FFNet), "const ff_ode*": C.POINTER(_abi.FFOde),
+             "ff_kernel_plan_info*": C.POINTER(_abi.FFKernelPlanInfo), **dict.fromkeys(data, C.c_void_p)}
+    parsed = {}
+    for ret, name, params in protos:
+        spellings = [re.sub(r"\s*\*", "*", re.sub(r"\w+$", "", " ".join(p.split())).strip()) for p in params.split(",") if p.strip() != "void"]
+        for t in [ret] + spellings:
+            assert t in ctype, f"{name}: the C type {t!r} is not in this test's dictionary"
+        parsed[name] = (ctype[ret], tuple(ctype[t] for t in spellings))
+    assert list(parsed) == list(_abi.SIGNATURES)      # the header's order
+    for name, sig in parsed.items():      # ... and bind() has put it on the library
+        assert _abi.SIGNATURES[name] == sig == (getattr(_lib.lib(), name).restype, tuple(getattr(_lib.lib(), name).argtypes)), name
+
+
+def test_typed_calls_take_plain_numbers_and_refuse_wrong_types():
+    """With argtypes set, plain Python numbers reach the library as the C types of the header, and a wrong type is an error of the
+    call instead of a silent 32-bit int.  No GPU: every call is refused before any launch."""
+    import ctypes as C
+    from fermiflow_amd import _abi, _lib
+    lib = _lib.lib()
+    assert lib.ff_potential(None, 4, 0, 2, 1.0, 1, None, None) == 1
+    for bad in ("4", 4.0):      # int64_t B
+        with pytest.raises(C.ArgumentError):
+            lib.ff_potential(None, bad, 0, 2, 1.0, 1, None, None)
+    with pytest.raises(C.ArgumentError):      # const ff_net*: another struct
+        lib.ff_backflow_v_div(None, 4, 6, 2, C.byref(_abi.FFOde()), None, None, None)
+    assert lib.ff_backflow_v_div(None, 4, 6, 2, C.byref(_abi.FFNet()), None, None, None) == 1
+    with pytest.raises(TypeError):      # FFOde by field name: all of them, no others
+        _abi.ode_struct(t0=0.0, t1=1.0)
+    # a size past 2^32 comes back whole (configs[4]); csrc/ff_eloc_ws.h: z(t0) (B,M) | Jt (B,M,M) | kbar, dDelta, lap parts (B,M) each |
+    # Delta (B) | Slater table (B, nq) | 2 counters, nq = M + d (d + 1) / 2 n + d n^2 + 2
+    B, n, d, M = 131072, 20, 3, 60
+    doubles = B * (M * M + 4 * M + 1 + (M + d * (d + 1) // 2 * n + d * n * n + 2)) + 2
+    assert lib.ff_eloc_workspace_bytes(B, n, d) == 8 * doubles > 2**32
+
+
+def test_signatures_and_struct_mirrors_are_declared_in_one_place():
+    """No restype / argtypes assignment and no ctypes mirror of ff_net / ff_ode outside fermiflow_amd/_abi.py, in the package, the tests
+    and the tools: a second declaration is one that can be forgotten."""
+    found = {}
+    for top in ("fermiflow_amd", "tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, top)):
+            for path in (os.path.join(dirpath, f) for f in files if f.endswith(".py")):
+                src = open(path).read()
+                hits = re.findall(r"\.(?:restype|argtypes)\b[^=\n]*=(?!=)", src) + [
+                    m for m in re.findall(r"^class\s+\w+\s*\([^)]*Structure[^)]*\)\s*:.*?(?=^\S|\Z)", src, flags=re.S | re.M)
+                    if re.search(r"\b(ew1|walker_cost)\b", m)]
+                if hits:
+                    found[os.path.relpath(path, ROOT)] = hits
+    assert list(found) == [os.path.join("fermiflow_amd", "_abi.py")] and len(found[os.path.join("fermiflow_amd", "_abi.py")]) == 3, found
 
 
 def test_no_cpu_fallback():

@@ -146,5 +146,4 @@ def test_refusals_write_nothing():
         assert st == status, (kw, st)
         assert lib.ff_last_error().decode().startswith("ff_observe:"), lib.ff_last_error()
         assert np.array_equal(acc, before)
-    lib.ff_observe_buffer_bytes.restype = __import__("ctypes").c_size_t
     assert lib.ff_observe_buffer_bytes(0) == 0 and lib.ff_observe_buffer_bytes(1025) == 0

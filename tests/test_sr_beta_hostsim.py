@@ -1,6 +1,5 @@
 """Per-state moments of the scores under the host simulator (ff_sr_state_moments / ff_sr_state_finish: csrc/ff_sr.h).
 CPU only; the symbols are called through simlib.lib() with ctypes (tests/sr_beta_ref.py)."""
-import ctypes as C
 import hashlib
 
 import numpy as np
@@ -93,19 +92,18 @@ def test_nan_row_poisons_the_sums_it_enters():
 def test_refusals():
     lib = S.lib()
     err = lambda: lib.ff_last_error().decode()
-    lib.ff_sr_state_moments_workspace_bytes.restype = C.c_size_t
     for P, ns in ((0, 3), (1537, 3), (8, 0)):
-        assert lib.ff_sr_state_moments_workspace_bytes(C.c_int64(8), P, ns) == 0
+        assert lib.ff_sr_state_moments_workspace_bytes(8, P, ns) == 0
         st, sums = RB.sim_state_moments(S, np.ones((8, P)), np.ones(8), np.zeros(8, dtype=np.int32), np.ones(max(ns, 1)), check=False, ns=ns)
         assert st == 2 and err().startswith("ff_sr:"), (P, ns, st, err())
         assert np.isnan(sums).all()      # nothing was launched
         f = np.full(4, 7.0)
         assert lib.ff_sr_state_finish(None, P, ns, S._p(f), S._p(f), S._p(f), S._p(f), S._p(f)) == 2 and err().startswith("ff_sr:")
         assert (f == 7.0).all()
-    assert lib.ff_sr_state_moments_workspace_bytes(C.c_int64(-1), 300, 3) == 0
-    assert lib.ff_sr_state_moments_workspace_bytes(C.c_int64(8), 1536, 4096) > 0
+    assert lib.ff_sr_state_moments_workspace_bytes(-1, 300, 3) == 0
+    assert lib.ff_sr_state_moments_workspace_bytes(8, 1536, 4096) > 0
     f = np.zeros(8)
-    assert lib.ff_sr_state_moments(None, C.c_int64(4), 2, 1, None, S._p(f), S._p(f), S._p(f), S._p(f), S._p(f)) == 1 and err().startswith("ff_sr:")
+    assert lib.ff_sr_state_moments(None, 4, 2, 1, None, S._p(f), S._p(f), S._p(f), S._p(f), S._p(f)) == 1 and err().startswith("ff_sr:")
 
 
 @pytest.mark.parametrize("B,P", R.MOMENT_CASES, ids=[f"B{B}_P{P}" for B, P in R.MOMENT_CASES])

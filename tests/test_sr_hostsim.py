@@ -1,7 +1,6 @@
 """Per-walker scores and their moments under the host simulator (ff_cnf_adjoint_scores: csrc/ff_cnf_adj.hip and
 ff_adj_direct_body.inc with SCORES; ff_sr_moments / ff_sr_finish: csrc/ff_sr.h).  CPU only; the symbols are called
 through simlib.lib() with ctypes (tests/sr_ref.py)."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -129,17 +128,16 @@ def test_refusals(golden):
     assert st == 1 and err().startswith("ff_scores:")
     st, sc, _ = R.sim_scores(S, z[:0], z[:0], net, R.LOOSE)      # B = 0: a no-op
     assert st == 0
-    lib.ff_sr_moments_workspace_bytes.restype = C.c_size_t
     for P in (0, 1537):
-        assert lib.ff_sr_moments_workspace_bytes(C.c_int64(8), P) == 0
+        assert lib.ff_sr_moments_workspace_bytes(8, P) == 0
         st, sums = R.sim_moments(S, np.ones((8, P)), np.ones(8), 0.0, check=False)
         assert st == 2 and err().startswith("ff_sr:"), (P, st, err())
         assert np.isnan(sums).all()
-    assert lib.ff_sr_moments_workspace_bytes(C.c_int64(-1), 300) == 0
-    assert lib.ff_sr_moments_workspace_bytes(C.c_int64(8), 1536) > 0
+    assert lib.ff_sr_moments_workspace_bytes(-1, 300) == 0
+    assert lib.ff_sr_moments_workspace_bytes(8, 1536) > 0
     f = np.zeros(4)
     assert lib.ff_sr_finish(None, 0, S._p(f), S._p(f), S._p(f), S._p(f)) == 2 and err().startswith("ff_sr:")
-    assert lib.ff_sr_moments(None, C.c_int64(4), 2, None, S._p(f), S._p(f), S._p(f), S._p(f)) == 1 and err().startswith("ff_sr:")
+    assert lib.ff_sr_moments(None, 4, 2, None, S._p(f), S._p(f), S._p(f), S._p(f)) == 1 and err().startswith("ff_sr:")
 
 
 @pytest.mark.parametrize("B,P", R.MOMENT_CASES, ids=[f"B{B}_P{P}" for B, P in R.MOMENT_CASES])

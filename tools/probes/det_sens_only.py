@@ -25,7 +25,7 @@ for (nup, ndn, dim) in ((12, 12, 2), (10, 10, 3), (7, 6, 2)):
     net, x, tu, td = setup(nup, ndn, dim)
     B, n = x.shape[0], nup + ndn
     M = n * dim
-    nb = L.lib().ff_eloc_workspace_bytes(L.i64(B), n, dim)
+    nb = L.lib().ff_eloc_workspace_bytes(B, n, dim)
     for mode in ("sensitivities only", "whole ff_eloc_nd"):
         evs, zs = [], []
         for it in range(NRUN):
@@ -33,7 +33,7 @@ for (nup, ndn, dim) in ((12, 12, 2), (10, 10, 3), (7, 6, 2)):
                 ws = torch.empty(nb // 8, dtype=torch.float64, device=dev)
                 st = torch.zeros(32, dtype=torch.int32, device=dev)
                 o = L.ode(0.0, 1.0, 1e-8, 1e-10)
-                L.check(L.lib().ff_eloc_sensitivities(L.stream(), L.i64(B), n, dim, net.ref(), C.byref(o), L.ptr(x), L.ptr(ws), L.ptr(st)), "sens")
+                L.check(L.lib().ff_eloc_sensitivities(L.stream(), B, n, dim, net.ref(), C.byref(o), L.ptr(x), L.ptr(ws), L.ptr(st)), "sens")
                 z = ws[:B * M].clone(); ev = int(st[0])
             else:
                 r = native.eloc(tu, td, nup, ndn, net, x, 0.0, 1.0, 1e-8, 1e-10, 2.0, True, want_stats=True)

@@ -67,12 +67,12 @@ def main():
     fr_ch[0] = z
 
     def one_call():
-        L.check(lib.ff_cnf_generate_frames(st, L.i64(B), n, d, net.ref(), C.byref(ode_all), L.ptr(z), K, L.ptr(fr_one), L.ptr(st_one)), "frames")
+        L.check(lib.ff_cnf_generate_frames(st, B, n, d, net.ref(), C.byref(ode_all), L.ptr(z), K, L.ptr(fr_one), L.ptr(st_one)), "frames")
         return fr_one, st_one
 
     def chained():
         for k in range(1, K):
-            L.check(lib.ff_cnf_generate(st, L.i64(B), n, d, net.ref(), C.byref(odes[k - 1]), L.ptr(fr_ch[k - 1]), L.ptr(fr_ch[k]), L.ptr(st_ch)), "generate")
+            L.check(lib.ff_cnf_generate(st, B, n, d, net.ref(), C.byref(odes[k - 1]), L.ptr(fr_ch[k - 1]), L.ptr(fr_ch[k]), L.ptr(st_ch)), "generate")
         return fr_ch, st_ch
 
     res = {"device": torch.cuda.get_device_name(0), "library": _lib.LIB_PATH, "walkers": B, "nframes": K, "runs": RUNS}

@@ -63,7 +63,7 @@ def main():
         tm = statistics.median(timed(mom) for _ in range(reps))
         out.update(moments_ms=tm, moments_tflops=2.0 * B * P * P / tm * 1e-9, moments_peak_fraction=2.0 * B * P * P / tm * 1e-9 / 78.6,
                    moments_design_bytes_over_scores_bytes=(8.0 * B * 128 * (((P + 63) // 64) * ((P + 63) // 64 + 1) // 2)
-                                                           + 2.0 * L.lib().ff_sr_moments_workspace_bytes(L.i64(B), P)) / (8.0 * B * P))
+                                                           + 2.0 * L.lib().ff_sr_moments_workspace_bytes(B, P)) / (8.0 * B * P))
         from fermiflow_amd.utils import make_adam
         adam, sr = make_adam(model.parameters(), lr=1e-2), ff.SR(model.parameters())
 

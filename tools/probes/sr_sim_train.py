@@ -12,7 +12,6 @@ ff_sr_state_finish, numpy's solves for both blocks.  Prints F per iteration and 
 import os
 import sys
 
-import ctypes as C
 
 import numpy as np
 
@@ -76,8 +75,7 @@ def main_beta(argv):
         p = np.exp(logits - logits.max()); p /= p.sum()
         ws = np.sort(rng.choice(ns, size=B, p=p)).astype(np.int32)
         z = np.empty((B, 3, 2)); lp = np.empty(B); cnt = np.empty(B, dtype=np.int32)
-        S._ck(S.lib().ff_mcmc_sample(None, C.c_int64(B), 3, 0, S._p(tab), None, S._p(ws), 100, C.c_double(0.1), C.c_uint64(1000 + it),
-                                     C.c_int64(0), S._p(z), S._p(lp), S._p(cnt)))
+        S._ck(S.lib().ff_mcmc_sample(None, B, 3, 0, S._p(tab), None, S._p(ws), 100, 0.1, 1000 + it, 0, S._p(z), S._p(lp), S._p(cnt)))
         x, _ = S.cnf_generate(z, net, **tol)
         r = S.eloc(x, 3, 0, net, Z, tab_up=tab, wstate=ws, **tol)
         e = r["eloc"]
