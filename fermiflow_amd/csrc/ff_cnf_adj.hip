@@ -162,19 +162,24 @@ struct ff_rec { double dr, ca, cb; int j; };
 // add one coefficient row to node j of net t: LDS table for the near nodes, global overflow table beyond
 // (one branch and one address computation per row, not per coefficient)
 // nrow (wave-uniform: header slot 5 of the radial table, ff_radial.h): the coefficients the weights of this launch need -- 6, 8, 10 or all
-// 12; an LDS floating-point atomic is served at less than one lane per clock and CU, so the rows are no longer than they have to be
-FF_D void ff_row_add(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict__ ovf, int t, int j, const double* c, int nrow) {
+// 12; an LDS floating-point atomic is served at less than one lane per clock and CU, so the rows are no longer than they have to be.
+// NEXP >= nrow: the coefficients the caller has expanded into c.  A row of the global overflow table always takes all FF_DEP_ROW
+// coefficients: `rest` fills c[NEXP ..] there -- the callers expand no further than NEXP until a node beyond the LDS table (r >= 8)
+// asks for the rest.
+template <int NEXP, typename Rest>
+FF_D void ff_row_add(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict__ ovf, int t, int j, double* c, int nrow, Rest rest) {
   if (j < FF_DEP_NLDS) {
     double* row = &sW[t][j][0];
 #pragma unroll
     for (int k = 0; k < 6; k++) atomicAdd(row + k, c[k]);
 #pragma unroll
-    for (int k0 = 6; k0 < FF_DEP_ROW; k0 += 2) {
+    for (int k0 = 6; k0 < NEXP; k0 += 2) {
       if (nrow > k0) { atomicAdd(row + k0, c[k0]); atomicAdd(row + k0 + 1, c[k0 + 1]); }
     }
   } else {
     // (hipcc otherwise sinks the two atomic loops into one over a select of an LDS and a global pointer -- a flat pointer
     // whose aperture test it then fails to encode: "Illegal instruction detected" in the one-walker-per-wave kernels)
+    rest();
     double* row = ovf + ((size_t)t * FF_DEP_NTOT + j) * FF_DEP_ROW;
 #pragma unroll
     for (int k = 0; k < FF_DEP_ROW; k++) atomicAdd(row + k, c[k]);
@@ -183,16 +188,24 @@ FF_D void ff_row_add(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict_
   }
 }
 
-FF_D void ff_deposit(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict__ ovf, int t, const ff_rec& rc, double w, int nrow) {
-  if (w == 0.0) return;
-  double pk = 1.0, pm = 0.0, c[FF_DEP_ROW];   // dr^k/k!, dr^(k-1)/(k-1)!
+// coefficients K0 <= k < K1 of one record, scaled by w:  c[k] = w (ca dr^k/k! + cb dr^(k-1)/(k-1)!)
+template <int K0, int K1>
+FF_D void ff_dep_expand1(const ff_rec& rc, double w, double* c) {
+  double pk = 1.0, pm = 0.0;   // dr^k/k!, dr^(k-1)/(k-1)!
 #pragma unroll
-  for (int k = 0; k < FF_DEP_ROW; k++) {
-    c[k] = w * fma(rc.ca, pk, rc.cb * pm);
+  for (int k = 0; k < K1; k++) {
+    if (k >= K0) c[k] = w * fma(rc.ca, pk, rc.cb * pm);
     pm = pk;
     pk = pk * rc.dr * (1.0 / (k + 1));
   }
-  ff_row_add(sW, ovf, t, rc.j, c, nrow);
+}
+
+template <int NEXP>
+FF_D void ff_deposit(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict__ ovf, int t, const ff_rec& rc, double w, int nrow) {
+  if (w == 0.0) return;
+  double c[FF_DEP_ROW];
+  ff_dep_expand1<0, NEXP>(rc, w, c);
+  ff_row_add<NEXP>(sW, ovf, t, rc.j, c, nrow, [&]() { ff_dep_expand1<NEXP, FF_DEP_ROW>(rc, w, c); });
 }
 
 // The five records of one accepted step (stages 0, 2, 3, 4, 5 with the b-weights of the tableau).  Within a step the radius moves a
@@ -203,6 +216,9 @@ FF_D void ff_deposit(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict_
 // more than 0.19 within one step: rare; the branch is skipped when no lane of the wave needs it) goes separately about its own node.
 // Truncation: the expansion is of order 11 in w1 dr with |dr| <= 1.5 h_d here, and the table is declared usable only while
 // max|w1| h_d <= 0.4 (ff_radial.h: 0.6 while |dr| <= h_d / 2 ... h_d) -- (0.6)^12 / 12! as before.
+// The expansions are NEXP coefficients long (8 when the rows are): the products of the coefficients kept, and of the full row where the
+// overflow table takes it, are those of the twelve-coefficient expansion in its order.
+template <int NEXP>
 FF_D void ff_deposit5(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict__ ovf, int t, const ff_rec& q0, const ff_rec& q2,
                       const ff_rec& q3, const ff_rec& q4, const ff_rec& q5, double hw, int nrow) {
   if (hw == 0.0) return;
@@ -218,22 +234,27 @@ FF_D void ff_deposit5(double (*sW)[FF_DEP_NLDS][FF_DEP_LROW], double* __restrict
   double acc[FF_DEP_ROW];
 #pragma unroll
   for (int k = 0; k < FF_DEP_ROW; k++) acc[k] = 0.0;
+  // coefficients K0 <= k < K1 of the records near the centre, added to acc in the order of the records
+  auto near = [&](auto k0_tag, auto k1_tag, bool far_too) {
+    constexpr int K0 = decltype(k0_tag)::value, K1 = decltype(k1_tag)::value;
 #pragma unroll
-  for (int e = 0; e < 5; e++) {
-    const double dr = fma((double)(rc[e]->j - jC), HD, rc[e]->dr);
-    if (fabs(dr) <= 1.5 * HD) {
-      double pk = bw[e], pm = 0.0;      // w dr^k/k!, w dr^(k-1)/(k-1)!
+    for (int e = 0; e < 5; e++) {
+      const double dr = fma((double)(rc[e]->j - jC), HD, rc[e]->dr);
+      if (fabs(dr) <= 1.5 * HD) {
+        double pk = bw[e], pm = 0.0;      // w dr^k/k!, w dr^(k-1)/(k-1)!
 #pragma unroll
-      for (int k = 0; k < FF_DEP_ROW; k++) {
-        acc[k] += fma(rc[e]->ca, pk, rc[e]->cb * pm);
-        pm = pk;
-        pk = pk * dr * (1.0 / (k + 1));
+        for (int k = 0; k < K1; k++) {
+          if (k >= K0) acc[k] += fma(rc[e]->ca, pk, rc[e]->cb * pm);
+          pm = pk;
+          pk = pk * dr * (1.0 / (k + 1));
+        }
+      } else if (far_too) {
+        ff_deposit<NEXP>(sW, ovf, t, *rc[e], bw[e], nrow);
       }
-    } else {
-      ff_deposit(sW, ovf, t, *rc[e], bw[e], nrow);
     }
-  }
-  ff_row_add(sW, ovf, t, jC, acc, nrow);
+  };
+  near(ff_stage_c<0>{}, ff_stage_c<NEXP>{}, true);
+  ff_row_add<NEXP>(sW, ovf, t, jC, acc, nrow, [&]() { near(ff_stage_c<NEXP>{}, ff_stage_c<FF_DEP_ROW>{}, false); });
 }
 
 #ifndef FF_ADJ_WPS
@@ -271,6 +292,7 @@ ff_ode_adjtab_kernel(ff_adj_args A) {
   __shared__ double s_W[2][FF_DEP_NLDS][FF_DEP_LROW];
   __shared__ int s_pa[R], s_pb[R], s_any_[WPW];
   __shared__ int s_turn, s_done[2];
+  __shared__ double s_nil[D];   // zeros: the "partner" a one-body radius subtracts (x - 0 = x, as the select it replaces gave)
 
   const int wv = WPW > 1 ? (int)(threadIdx.x >> 6) : 0, lane = threadIdx.x & (FF_WAVE - 1);
   auto& s_z = s_z_[wv]; auto& s_kb = s_kb_[wv]; auto& s_err = s_err_[wv]; auto& s_ad = s_ad_[wv]; auto& s_hw = s_hw_[wv];
@@ -280,6 +302,11 @@ ff_ode_adjtab_kernel(ff_adj_args A) {
   const int gg = ingrp ? g : 0;
   const int ai = i / D, ci = i % D;
   for (int e = threadIdx.x; e < 2 * FF_DEP_NLDS * FF_DEP_LROW; e += FF_WAVE * WPW) (&s_W[0][0][0])[e] = 0.0;
+  // Without a one-body net (Hm == 0) no phase ever writes the diagonal entries s_T[g][a][a * 3 D ..], and the component phase reads
+  // them all the same, times its factor 0: they must hold finite numbers, so the buffer is zeroed here, once -- fma(0, +0, acc) = acc
+  // is what the select `use ? t : 0.0` gave, and holds only as long as nothing writes those entries
+  for (int e = threadIdx.x; e < WPW * G * N * TROW; e += FF_WAVE * WPW) (&s_T_[0][0][0][0])[e] = 0.0;
+  if (threadIdx.x < D) s_nil[threadIdx.x] = 0.0;
   if (threadIdx.x == 0) {
     int p = 0;
     for (int a = 0; a < N; a++)
@@ -303,6 +330,16 @@ ff_ode_adjtab_kernel(ff_adj_args A) {
     const int qg = act ? q / nrad : 0, p = act ? q - qg * nrad : 0;
     rq_id[sl] = act ? (qg | (s_pa[p] << 4) | ((s_pb[p] < 0 ? 15 : s_pb[p]) << 8) | (p << 12)) : -1;
   }
+  // per radius, fixed for the launch: 2 for a pair and 1 for a one-body radius -- an exact factor where selects between the two
+  // forms of a record stood
+  double rq_kc[NSLOT];
+#pragma unroll
+  for (int sl = 0; sl < NSLOT; sl++) rq_kc[sl] = (rq_id[sl] >= 0 && ((rq_id[sl] >> 8) & 15) != 15) ? 2.0 : 1.0;
+  // per partner j of this lane's particle, fixed for the launch: the sign its entry of T is read with (the pair (j, ai) sits in row
+  // min(j, ai): written from the lower particle's side), zero for the one-body entry of a flow without a one-body net
+  double cp_sg[N];
+#pragma unroll
+  for (int j = 0; j < N; j++) cp_sg[j] = (has_mu || j != ai) ? (j < ai ? -1.0 : 1.0) : 0.0;
   bool off_any = false;
   constexpr double NT = 2 * M;
   const int64_t ngroups = (A.B + G - 1) / G;
@@ -418,11 +455,13 @@ ff_ode_adjtab_kernel(ff_adj_args A) {
         const int qg = act ? (id & 15) : 0, a = act ? ((id >> 4) & 15) : 0, bq = act ? ((id >> 8) & 15) : 15;
         const bool pair = bq != 15;
         const int bb = pair ? bq : a;
+        const double* zb = pair ? &s_z[qg][bb * D] : s_nil;
+        const double* kb = pair ? &s_kb[qg][bb * D] : s_nil;
         double r2 = 0.0;
 #pragma unroll
         for (int c = 0; c < D; c++) {
-          rq_rho[sl][c] = s_z[qg][a * D + c] - (pair ? s_z[qg][bb * D + c] : 0.0);
-          rq_dl[sl][c] = s_kb[qg][a * D + c] - (pair ? s_kb[qg][bb * D + c] : 0.0);
+          rq_rho[sl][c] = s_z[qg][a * D + c] - zb[c];
+          rq_dl[sl][c] = s_kb[qg][a * D + c] - kb[c];
           r2 = fma(rq_rho[sl][c], rq_rho[sl][c], r2);
         }
         ff_sqrt_rcp(r2, rq_r[sl], rq_ri[sl]);
@@ -451,11 +490,15 @@ ff_ode_adjtab_kernel(ff_adj_args A) {
           jf = fmin(jf, (double)(FF_DEP_NTOT - 1));
           cur[sl].j = (r == r) ? (int)jf : 0;
           cur[sl].dr = fma(-jf, 1.0 / FF_DEP_INVH, r);
-          cur[sl].ca = pair ? -(al - 2.0 * D * ad) : -(al - D * ad);
-          cur[sl].cb = pair ? 2.0 * ad * r : ad * r;
+          // pair: -(al - 2 D ad), one-body: -(al - D ad).  For D a power of two the products D ad and 2 (D ad) are exact, so the factor
+          // form rounds once, in the subtraction, like either side of the select, contracted or not.  For D = 3 a contraction fuses
+          // the product 6 ad or 3 ad into the subtraction, which 2 x (the rounded 3 ad) is not: the select stays there
+          if constexpr ((D & (D - 1)) == 0) cur[sl].ca = -(al - rq_kc[sl] * (D * ad));
+          else cur[sl].ca = pair ? -(al - 2.0 * D * ad) : -(al - D * ad);
+          cur[sl].cb = rq_kc[sl] * ad * r;
           // own rows: +x to particle a from partner bb, -x to particle bb from partner a
           const double f0 = hd[0], f1 = hd[1], f2 = hd[2];
-          const double F1 = f1 * (al * ri), gq = (pair ? 2.0 : 1.0) * fma(f2, r, (1.0 + D) * f1) * ri;
+          const double F1 = f1 * (al * ri), gq = rq_kc[sl] * fma(f2, r, (1.0 + D) * f1) * ri;
           // ONE entry per radius, in the row of its first particle (a < bb): the lanes of particle bb read it there with the other sign
           // (round 6: six LDS stores per pair where the mirrored entry took twelve -- this kernel, too, lives on the LDS)
           double* Ta = &s_T[qg][a][bb * 3 * D];
@@ -475,12 +518,11 @@ ff_ode_adjtab_kernel(ff_adj_args A) {
         double vi = 0.0, dvk = 0.0, gdi = 0.0;
 #pragma unroll
         for (int j = 0; j < N; j++) {
-          const bool use = has_mu || j != ai;
           const bool lower = j < ai;      // the pair (j, ai) sits in row j, slot ai, written from particle j's side: the other sign
           const double* T = lower ? &s_T[gg][j][ai * 3 * D + ci] : &s_T[gg][ai][j * 3 * D + ci];
-          const double sg = lower ? -1.0 : 1.0;
+          const double sg = cp_sg[j];
           const double tv = T[0], tw = T[D], tg = T[2 * D];
-          vi = fma(sg, use ? tv : 0.0, vi); dvk = fma(sg, use ? tw : 0.0, dvk); gdi = fma(sg, use ? tg : 0.0, gdi);
+          vi = fma(sg, tv, vi); dvk = fma(sg, tw, dvk); gdi = fma(sg, tg, gdi);
         }
         out[0] = vi;
         out[1] = fma(s_ad[gg], gdi, -dvk);
@@ -592,7 +634,9 @@ ff_ode_adjtab_kernel(ff_adj_args A) {
             const int t = ((rq_id[sl] >> 8) & 15) != 15 ? 0 : 1;
             const double hw = s_hw[qg];
 #ifndef FF_ADJ_NODEP      // (timing experiments only: the parameter gradient is then wrong)
-            ff_deposit5(s_W, ovf, t, r0[sl], r2[sl], r3[sl], r4[sl], r5[sl], hw, dep_nrow);
+            // (wave-uniform.  Two expansion lengths: every length its own copy of the deposit cost the kernel thirteen registers)
+            if (dep_nrow == 8) ff_deposit5<8>(s_W, ovf, t, r0[sl], r2[sl], r3[sl], r4[sl], r5[sl], hw, 8);
+            else ff_deposit5<FF_DEP_ROW>(s_W, ovf, t, r0[sl], r2[sl], r3[sl], r4[sl], r5[sl], hw, dep_nrow);
 #endif
             if (hw != 0.0) r0[sl] = r6[sl];   // FSAL: the record of k6 opens that walker's next step
           }
