@@ -99,6 +99,26 @@ template <int V> struct ff_stage_c { static constexpr int value = V; };
 #define FF_D __device__ __forceinline__
 #define FF_HD __host__ __device__ __forceinline__
 
+// The argument struct of a kernel whose ONE parameter it is, read again from the kernel-argument segment through a pointer the
+// compiler cannot see through.  A kernel at its register budget keeps every argument it uses behind its main loop in a scalar
+// register across that loop, and where those run out, in the lanes of a vector register: one lane move per value and use
+// (ff_eloc_mfma_kernel: 643 of them around the evaluation loop).  Read through this pointer where they are used, the
+// values are scalar loads from memory that is resident anyway, and only the pointer crosses the loop.
+#ifndef FF_KERNARGS
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FF_CONST_AS __attribute__((address_space(4)))
+template <class T>
+FF_D const FF_CONST_AS T* ff_kernargs() {
+  const FF_CONST_AS T* q = (const FF_CONST_AS T*)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(q));
+  return q;
+}
+#define FF_KERNARGS(T, A) ff_kernargs<T>()
+#else
+#define FF_KERNARGS(T, A) (&(A))
+#endif
+#endif
+
 // status codes of the C ABI
 #define FF_OK 0
 #define FF_EINVAL 1        // invalid argument (null pointer, non-positive size, ...)

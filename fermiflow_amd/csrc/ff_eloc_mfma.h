@@ -30,7 +30,8 @@
 //   The six stages of a Dormand-Prince step are six instantiations of the evaluation (compile-time stage: DESIGN.md 3s).
 //   S takes the place of A in LDS once the last operand of J' = A J has been read (one wave per workgroup: program order).
 //   The component 4c + r of grad Delta sits on lane (r, c) (it comes out of the transposed blocks by a quad reduction).
-// 14 KB of LDS and 236 registers: two waves per SIMD (the vector pipe issues at half rate for a single wave).
+// 14 KB of LDS and 253 registers (table kernel, six particles): two waves per SIMD (the vector pipe issues at half rate for a single
+// wave).
 #pragma once
 
 // Dormand-Prince vector of a lane whose components 1 .. NB (the J blocks) live in lane-private LDS columns and whose other
@@ -123,7 +124,6 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
   const double rtol = A.rtol, atol = A.atol;
   double (*s_gd)[MP] = s_z;
   constexpr double NT = (double)M * M + 4.0 * M + 2.0;   // z, J, kbar, grad Delta, Delta, lap Delta
-  const int64_t ngroups = (A.B + G - 1) / G;
   // Pair radii this lane evaluates for its own walker (slot qk: pair i16 + 16 qk): a | b << 4 | record offset << 8.  The ONE-BODY
   // radius of a particle is evaluated by that particle's own row lanes (both of them, redundantly) and applied from registers: no
   // record, no second radius slot at six particles -- per wave-evaluation seven LDS stores and six loads less on a kernel that is
@@ -173,22 +173,27 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
 #endif
 #endif
   for (int64_t grp = blockIdx.x;; grp += gridDim.x) {
-    if (A.queue) {   // persistent grid: next group from the launch's work counter (the order is by schedule key: cost class + 4 x planned steps, costliest first)
+    // What the head of a walker group needs of the arguments comes from the argument segment again, by scalar loads (FF_KERNARGS,
+    // ff_common.h), as does the finish behind the evaluation loop: kept in scalar registers across that loop, these values were parked
+    // in vector lanes and came back by 106 + 480 lane reads per group
+    const auto* Ah = FF_KERNARGS(ff_fwd_args, A);
+    if (Ah->queue) {   // persistent grid: next group from the launch's work counter (the order is by schedule key: cost class + 4 x planned steps, costliest first)
       FF_WG1_SYNC();
-      if (lane == 0) s_next = (long long)atomicAdd(A.queue + (TAB ? 0 : 1), 1ULL);
+      if (lane == 0) s_next = (long long)atomicAdd(Ah->queue + (TAB ? 0 : 1), 1ULL);
       FF_WG1_SYNC();
       grp = s_next;
     }
-    if (grp >= ngroups) break;
+    if (grp >= (Ah->B + G - 1) / G) break;
     // which walker this lane serves: derived from the (scalar) group index wherever it is needed -- here and again behind the
     // evaluation loop -- so that no per-lane copy of it is live through the loop (at 256 registers such values are spilled around it:
     // with the fused finish the scratch traffic of ~50 of them showed as 120 MB of HBM writes per launch)
-    auto walker_of = [&](int wq, int64_t& bw, bool& vw) {
+    auto walker_of = [&](const auto* Q, int wq, int64_t& bw, bool& vw) {
       const int64_t bq = grp * G + wq;
-      const bool inb = bq < A.B;
-      bw = ff_opt_load(A.order, inb, bq, A.y_in, (int32_t)bq);
+      const bool inb = bq < Q->B;
+      const double* const safe = Q->y_in;
+      bw = ff_opt_load(Q->order, inb, bq, safe, (int32_t)bq);
       // routing by cost class (launch_mfma): with heavy_mode = 2 the walkers of class >= heavy_class belong to another launch
-      vw = inb && !(A.heavy_mode == 2 && ff_opt_load(A.wclass, inb, bw, A.y_in, (int32_t)0) >= A.heavy_class);
+      vw = inb && !(Q->heavy_mode == 2 && ff_opt_load(Q->wclass, inb, bw, safe, (int32_t)0) >= Q->heavy_class);
     };
     int lgp = lane;
     FF_OPAQUE(lgp);
@@ -196,7 +201,7 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
     const bool owner = p < M;
     int64_t b;
     bool valid;
-    walker_of(w, b, valid);
+    walker_of(Ah, w, b, valid);
     // Dormand-Prince storage as in ff_ode_fwd_kernel: y, c0..c2 (k0..k2, then the inputs of stages 4, 5 and y_new), c3 (error)
     double c0[NV], c1[NV], c2[NV];
     // y in registers (round 6, late: with compile-time stages the kernel runs at 208 registers, and y's J blocks -- read from their LDS
@@ -207,20 +212,23 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
 #pragma unroll
     for (int v = 0; v < NV; v++) { y.set(v, 0.0); c0[v] = 0.0; c1[v] = 0.0; c2[v] = 0.0; c3.set(v, 0.0); }
     {
-      const double y0 = ff_opt_load(A.y_in, valid && owner, b * M + p, A.y_in, 0.25 * (p + 1) + 0.125 * ((p * 7) % 5));   // idle walkers: finite, distinct
+      const double* const yin = Ah->y_in;
+      const double y0 = ff_opt_load(yin, valid && owner, b * M + p, yin, 0.25 * (p + 1) + 0.125 * ((p * 7) % 5));   // idle walkers: finite, distinct
       if (owner) y.set(0, y0);
     }
 #pragma unroll
     for (int I = 0; I < MB; I++) y.set(1 + I * MB + I, (r == c && 4 * I + r < M) ? 1.0 : 0.0);   // J = identity
     {
       ctl_t C;
-      C.S.begin(A.ta, A.tb, valid);
+      C.S.begin(Ah->ta, Ah->tb, valid);
       // walkers of a low cost class: looser tolerance for the sensitivity components, larger first step (ff_ode.walker_class)
-      const bool loose = ff_opt_load(A.wclass, valid, b, A.y_in, (int32_t)0x7fffffff) <= A.sens_class;
-      C.hwarm = ff_opt_load(A.h_init, valid, A.h_scale < 0.0 ? 0 : b, A.y_in, 0.0) * (loose ? A.h_scale_loose : fabs(A.h_scale));
+      const double* const yin = Ah->y_in;
+      const double h_scale = Ah->h_scale;
+      const bool loose = ff_opt_load(Ah->wclass, valid, b, yin, (int32_t)0x7fffffff) <= Ah->sens_class;
+      C.hwarm = ff_opt_load(Ah->h_init, valid, h_scale < 0.0 ? 0 : b, yin, 0.0) * (loose ? Ah->h_scale_loose : fabs(h_scale));
       if (!(C.hwarm > 0.0)) C.hwarm = 0.0;
       // tolerance of the sensitivity components relative to the coordinates' (ff_ode.sens_tol): weight in the error norm
-      C.sens_w = loose ? A.sens_w : 1.0;
+      C.sens_w = loose ? Ah->sens_w : 1.0;
       C.hmax_acc = 0.0; C.h0v = 0.0; C.d1v = 0.0;
       FF_WG1_SYNC();
       s_ctl[w].get(C);
@@ -241,9 +249,12 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
       constexpr int SG = decltype(stage_tag)::value;
       auto at = [&](int k) -> bool { if constexpr (SG == FF_STAGE_DYN) return s == k; else return SG == k; };
       auto upto3 = [&]() -> bool { if constexpr (SG == FF_STAGE_DYN) return true; else return SG <= 3; };
-      // the lane indices are laundered once per evaluation: otherwise every LDS address below becomes a loop-invariant register
+      // Direct evaluation: the lane indices are laundered once per evaluation, otherwise every LDS address below becomes a loop-invariant
+      // register (those instantiations sit at 256 registers).  The table kernels have had registers to spare since their stages are
+      // compile-time constants (236 of 256 at five and six particles): there the addresses and the decoded lane fields ARE kept across
+      // the evaluations, seventeen registers for 63 integer and compare instructions of every stage body
       int ln = FF_LANE_SELF();
-      FF_OPAQUE(ln);
+      if constexpr (!TAB) FF_OPAQUE(ln);
       const int r = ln >> 4, w = (ln >> 2) & 3, c = ln & 3, p = 4 * r + c, tl = 16 * c + 4 * w + r;
       const bool owner = p < M;
       const int ra = owner ? p / D : 0, rc = owner ? p % D : 0;
@@ -756,7 +767,8 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
     // determinants: coefficient-table loads by a per-lane index and 256 registers -- inlined here it took 0.5 ms per launch.)
     bool fin_done = false;
     if constexpr (N % 2 == 0 && D == 2) {
-      if (A.fin.on & 1) {
+      const auto* Af = FF_KERNARGS(ff_fwd_args, A);
+      if (Af->fin.on & 1) {
         constexpr int NSF = N / 2;
         fin_done = true;
         int ln = lane;
@@ -765,7 +777,7 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
         const bool owner = p < M;
         int64_t b;
         bool valid;
-        walker_of(w, b, valid);
+        walker_of(Af, w, b, valid);
         {   // S = J J^T of the final J -> s_A[w]
           double Jt[NB];
           const double idn = r == c ? 1.0 : 0.0;
@@ -798,8 +810,9 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
         double* const fT = s_rec + w * FS + 2 * NSF * NSF + sp * 2 * NSF * NSF;
         int deg[2 * NSF];
         {
-          const int32_t* tab = sp ? A.fin.tab_dn : A.fin.tab_up;
-          const int st = (A.fin.wstate && valid) ? A.fin.wstate[b] : 0;
+          const int32_t* tab = sp ? Af->fin.tab_dn : Af->fin.tab_up;
+          const int32_t* const wstate = Af->fin.wstate;
+          const int st = (wstate && valid) ? wstate[b] : 0;
 #pragma unroll
           for (int j = 0; j < NSF; j++) ff_orb_decode(tab[st * NSF + j], deg[j], deg[NSF + j]);
         }
@@ -897,11 +910,13 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
         const double logpv = walker_sum(lp0 - (p == PDL ? y0 : 0.0));
         const double g2 = walker_sum(gradp * gradp);
         // V(x) = sum_{i<j} Z / r_ij + (1/2) sum_i r_i^2 on the radius lanes (src/potentials.py:13, 23-47)
-        const double xp = ff_opt_load(A.y_in, valid && owner, b * M + p, A.y_in, 0.25 * (p + 1) + 0.125 * ((p * 7) % 5));
+        const double* const yin = Af->y_in;
+        const double xp = ff_opt_load(yin, valid && owner, b * M + p, yin, 0.25 * (p + 1) + 0.125 * ((p * 7) % 5));
         FF_WG1_SYNC();
         if (owner) s_z[w][p] = xp;
         FF_WG1_SYNC();
         double vl = 0.0;
+        const double Zc = Af->fin.Z;
 #pragma unroll
         for (int qk = 0; qk < NQ; qk++) {
           int id = rq_id[qk];
@@ -916,32 +931,37 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
           }
           double rr, ri;
           ff_sqrt_rcp(r2, rr, ri);
-          vl += act ? A.fin.Z * ri : 0.0;
+          vl += act ? Zc * ri : 0.0;
         }
         // (the trap term is taken by the coordinate lanes)
-        if (A.fin.use_ho && owner) vl = fma(0.5 * xp, xp, vl);
+        if (Af->fin.use_ho && owner) vl = fma(0.5 * xp, xp, vl);
         const double Vv = walker_sum(vl);
         if (valid) {
           ctl_t C; C.get(s_ctl[w]);
           const ff_stepper& S = C.S;
           const bool failed = S.fail != 0;
           const double bad = failed ? __builtin_nan("") : 0.0;
+          // (every output pointer of the walker fetched here, together, and consumed at once)
+          double* const o_y = Af->y_out; double* const o_dl = Af->dl_out;
+          double* const o_grad = Af->fin.grad; double* const o_g0 = Af->fin.glogp0; double* const o_logp = Af->fin.logp;
+          double* const o_lap = Af->fin.lap; double* const o_V = Af->fin.V; double* const o_eloc = Af->fin.eloc;
+          double* const o_h = Af->h_out; int32_t* const o_cost = Af->wcost; const bool o_stats = Af->stats != nullptr;
           if (owner) {
-            A.y_out[b * M + p] = y0 + bad;
-            if (A.fin.grad) A.fin.grad[b * M + p] = gradp + bad;
-            if (A.fin.glogp0) A.fin.glogp0[b * M + p] = g0p + bad;
+            o_y[b * M + p] = y0 + bad;
+            if (o_grad) o_grad[b * M + p] = gradp + bad;
+            if (o_g0) o_g0[b * M + p] = g0p + bad;
           }
           if (p == PDL) {
-            A.dl_out[b] = y0 + bad;
-            if (A.fin.logp) A.fin.logp[b] = logpv + bad;
-            if (A.fin.lap) A.fin.lap[b] = lapv + bad;
-            if (A.fin.V) A.fin.V[b] = Vv;
-            if (A.fin.eloc) A.fin.eloc[b] = -0.25 * lapv - 0.125 * g2 + Vv + bad;
+            o_dl[b] = y0 + bad;
+            if (o_logp) o_logp[b] = logpv + bad;
+            if (o_lap) o_lap[b] = lapv + bad;
+            if (o_V) o_V[b] = Vv;
+            if (o_eloc) o_eloc[b] = -0.25 * lapv - 0.125 * g2 + Vv + bad;
           }
           if (r == 0 && c == 0) {
-            if (A.h_out) A.h_out[b] = C.hmax_acc > 0.0 ? C.hmax_acc : C.hwarm;
-            if (A.wcost) A.wcost[b] = S.nacc + S.nrej;
-            if (A.stats) { atomicAdd(&s_st[0], nev); atomicMax(&s_st[1], S.nacc); atomicAdd(&s_st[2], S.nrej); if (failed) atomicMax(&s_st[3], 1); }
+            if (o_h) o_h[b] = C.hmax_acc > 0.0 ? C.hmax_acc : C.hwarm;
+            if (o_cost) o_cost[b] = S.nacc + S.nrej;
+            if (o_stats) { atomicAdd(&s_st[0], nev); atomicMax(&s_st[1], S.nacc); atomicAdd(&s_st[2], S.nrej); if (failed) atomicMax(&s_st[3], 1); }
           }
         }
       }
@@ -954,7 +974,8 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
      const bool owner = p < M;
      int64_t b;
      bool valid;
-     walker_of(w, b, valid);
+     const auto* Ar = FF_KERNARGS(ff_fwd_args, A);
+     walker_of(Ar, w, b, valid);
      if (valid) {
       ctl_t C; C.get(s_ctl[w]);
       const ff_stepper& S = C.S;
@@ -962,23 +983,23 @@ ff_eloc_mfma_kernel(ff_fwd_args A) {
       const bool failed = S.fail != 0;
       const double bad = failed ? __builtin_nan("") : 0.0;   // failed integration -> NaN results (see ff_ode_fwd_kernel)
       if (owner) {
-        A.y_out[b * M + p] = y.get(0) + bad;
-        A.kbar[b * M + p] = y.get(IK);
-        A.dD[b * M + p] = y.get(IDD);
-        if (p > 0) A.Lpart[b * M + p] = 0.0;
+        Ar->y_out[b * M + p] = y.get(0) + bad;
+        Ar->kbar[b * M + p] = y.get(IK);
+        Ar->dD[b * M + p] = y.get(IDD);
+        if (p > 0) Ar->Lpart[b * M + p] = 0.0;
       }
-      if (p == PDL) A.dl_out[b] = y.get(0) + bad;
-      if (p == PLP) A.Lpart[b * M] = y.get(0);
+      if (p == PDL) Ar->dl_out[b] = y.get(0) + bad;
+      if (p == PLP) Ar->Lpart[b * M] = y.get(0);
 #pragma unroll
       for (int I = 0; I < MB; I++)
 #pragma unroll
         for (int K = 0; K < MB; K++) {
-          if (4 * I + r < M && 4 * K + c < M) A.Jt[(b * M + 4 * K + c) * M + 4 * I + r] = y.get(1 + I * MB + K);   // Jt[b][i][k] = dz_k/dx_i
+          if (4 * I + r < M && 4 * K + c < M) Ar->Jt[(b * M + 4 * K + c) * M + 4 * I + r] = y.get(1 + I * MB + K);   // Jt[b][i][k] = dz_k/dx_i
         }
       if (r == 0 && c == 0) {
-        if (A.h_out) A.h_out[b] = hmax_acc > 0.0 ? hmax_acc : hwarm;
-        if (A.wcost) A.wcost[b] = S.nacc + S.nrej;
-        if (A.stats) { atomicAdd(&s_st[0], nev); atomicMax(&s_st[1], S.nacc); atomicAdd(&s_st[2], S.nrej); if (failed) atomicMax(&s_st[3], 1); }
+        if (Ar->h_out) Ar->h_out[b] = hmax_acc > 0.0 ? hmax_acc : hwarm;
+        if (Ar->wcost) Ar->wcost[b] = S.nacc + S.nrej;
+        if (Ar->stats) { atomicAdd(&s_st[0], nev); atomicMax(&s_st[1], S.nacc); atomicAdd(&s_st[2], S.nrej); if (failed) atomicMax(&s_st[3], 1); }
       }
      }
     }
