@@ -84,7 +84,9 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
   __shared__ double s_e2[TAB ? 1 : 64];
   __shared__ double s_z[G][M], s_kb[G][M], s_err[G][M];
   constexpr bool JET = (MODE == 2);
-  __shared__ __attribute__((aligned(16))) double s_rr[JET ? 1 : G][JET ? 1 : R][2];   // radius and its reciprocal
+  // The tabulated flow kernel (and its frames twin) by instruction count, DESIGN.md 3z: everything behind LEAN is an exact identity
+  constexpr bool LEAN = (MODE == 0 && TAB);
+  __shared__ __attribute__((aligned(16))) double s_rr[(JET || LEAN) ? 1 : G][(JET || LEAN) ? 1 : R][2];   // radius and its reciprocal (MODE 1 reads them; MODE 0 with the direct heads writes them as it always did)
   __shared__ __attribute__((aligned(16))) double s_hd[JET ? 1 : G][JET ? 1 : R][NH];
   // MODE 2: one record per radius with everything about it that does not depend on the direction:
   //   rho (D), 1/r, eta, eta', eta'', A = c (eta'' r + (1+D) eta'), B = c (eta''' r + (2+D) eta''), c (eta' r + D eta)
@@ -102,6 +104,10 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
   constexpr int TROW = N * 3 * D + 1;                              // T row of one particle (padded likewise)
   static_assert(N * TROW <= M * QTW, "T must fit the transposition buffer");
   __shared__ __attribute__((aligned(16))) double s_qt[JET ? G * M * QTW : 1];
+  // LEAN: a slot of +0.0 that stands in for what a lane does not have -- the partner of a one-body radius (x - +0.0 is x, bit for
+  // bit), the head of a particle's term with itself (0.0 as the factor, as selected before) -- so that those LDS reads are
+  // unconditional reads through a per-lane address instead of masked reads under a saved exec mask
+  __shared__ double s_zero[LEAN ? (D > 2 ? D : 2) : 1];
   __shared__ int s_pa[R], s_pb[R], s_any;
   __shared__ double s_rmin[G][R];   // smallest value each radius took during the walker's integration (walker_cost)
   // lane-private LDS columns for y and the error accumulator; 4 workgroups still fit a CU's LDS up to 12 coordinates, and the
@@ -127,6 +133,7 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
     ff_load_weights(s_w, A.net, lane);
   }
   bool off_table = false;
+  if constexpr (LEAN) { if (lane < (D > 2 ? D : 2)) s_zero[lane] = 0.0; }
   if (lane == 0) {
     int p = 0;
     for (int a = 0; a < N; a++)
@@ -298,9 +305,11 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
         const bool pair = bq != 15;
         const int bb = pair ? bq : a;
         double r2 = 0.0;
+        const double* zpart = pair ? &s_z[qg][bb * D] : s_zero;      // (LEAN)
 #pragma unroll
         for (int c = 0; c < D; c++) {
-          rq_rho[qk][c] = s_z[qg][a * D + c] - (pair ? s_z[qg][bb * D + c] : 0.0);
+          if constexpr (LEAN) rq_rho[qk][c] = s_z[qg][a * D + c] - zpart[c];
+          else rq_rho[qk][c] = s_z[qg][a * D + c] - (pair ? s_z[qg][bb * D + c] : 0.0);
           if constexpr (JET) rq_dk[qk][c] = s_kb[qg][a * D + c] - (pair ? s_kb[qg][bb * D + c] : 0.0);
           r2 = fma(rq_rho[qk][c], rq_rho[qk][c], r2);
         }
@@ -309,8 +318,13 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
         rq_dr[qk] = 0.0;
         rq_ok[qk] = true;
         if constexpr (TAB) {
-          rq_ok[qk] = ff_table_fetch<NH>(rtab, tab_inv_h, tab_h, pair ? 0 : 1, rq_r[qk], rq_T[qk], rq_dr[qk]);
-          if (act && !rq_ok[qk]) off_table = true;
+          if constexpr (LEAN) {      // no branch around the loads: the row index clamped, `ok` a predicate
+            rq_ok[qk] = ff_table_fetch_always<NH>(rtab, tab_inv_h, tab_h, pair ? 0 : 1, rq_r[qk], rq_T[qk], rq_dr[qk]);
+            off_table |= act & !rq_ok[qk];
+          } else {
+            rq_ok[qk] = ff_table_fetch<NH>(rtab, tab_inv_h, tab_h, pair ? 0 : 1, rq_r[qk], rq_T[qk], rq_dr[qk]);
+            if (act && !rq_ok[qk]) off_table = true;
+          }
         }
       }
       // the full stage input is formed here, while the table rows requested above are on their way
@@ -326,7 +340,11 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
         const double* rho = rq_rho[qk];
         const double r = rq_r[qk], ri = rq_ri[qk];
         double hd[NH];
-        if constexpr (TAB) {
+        if constexpr (LEAN) {
+          ff_table_eval<NH>(rq_T[qk], rq_dr[qk], hd);
+#pragma unroll
+          for (int m = 0; m < NH; m++) hd[m] = rq_ok[qk] ? hd[m] : 0.0;
+        } else if constexpr (TAB) {
           if (rq_ok[qk]) ff_table_eval<NH>(rq_T[qk], rq_dr[qk], hd);
           else {
 #pragma unroll
@@ -336,8 +354,10 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
           heads(pair ? 0 : 1, r, hd);
         }
         if constexpr (!JET) {
-          s_rr[qg][p][0] = r;
-          s_rr[qg][p][1] = ri;
+          if constexpr (!LEAN) {
+            s_rr[qg][p][0] = r;
+            s_rr[qg][p][1] = ri;
+          }
 #pragma unroll
           for (int m = 0; m < NH; m++) s_hd[qg][p][m] = hd[m];
         } else {
@@ -476,7 +496,12 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
           const bool self = (bq == ai);
           const int lo = bq < ai ? bq : ai, hi = bq < ai ? ai : bq;
           const int p = self ? 0 : ff_pair_index(N, lo, hi);
-          vi = fma(self ? 0.0 : s_hd[gg][p][0], zc - sz[bq * D + ci], vi);
+          if constexpr (LEAN) {
+            const double* hp = self ? s_zero : &s_hd[gg][p][0];
+            vi = fma(*hp, zc - sz[bq * D + ci], vi);
+          } else {
+            vi = fma(self ? 0.0 : s_hd[gg][p][0], zc - sz[bq * D + ci], vi);
+          }
         }
         if (has_mu) vi = fma(s_hd[gg][P + ai][0], zc, vi);
       }

@@ -419,5 +419,15 @@ FF_D void ff_sincospi(double t, double* sn, double* cs) {
   *cs = ((k + 1) & 2) ? -c0 : c0;
 }
 
+// a ^ b ^ c: one v_bitop3_b32 (truth table 0x96) on gfx950 where the compiler emits two v_xor_b32 (the Philox rounds: 71 per
+// sampler step); the plain expression in the host pass and everywhere else -- the same word either way
+FF_D uint32_t ff_xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
+  return (uint32_t)__builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+  return a ^ b ^ c;
+#endif
+}
+
 // number of (i<j) pairs before row i for n particles; pair index of (i,j), i<j
 FF_HD int ff_pair_index(int n, int i, int j) { return i * (2 * n - i - 1) / 2 + (j - i - 1); }

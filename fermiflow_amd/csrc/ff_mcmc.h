@@ -8,8 +8,8 @@
 //   ff_mc_ratio_chain  Philox-fed, the same decision taken on the determinants of the polynomial parts of the orbitals
 // and three LAYOUTS say who holds which coordinates and how log p is formed from them:
 //   ff_mc_one_lane     one lane per walker                                          ff_mcmc_kernel<NU, ND, NOISE>
-//   ff_mc_spin_lanes   two lanes per walker, one per spin species (NU = ND = NS)    ff_mcmc_spin_kernel<NS, true>, ff_mcmc_spin_philox_kernel<NS>
-//   ff_mc_pair_lanes   two lanes per walker splitting the particles of ONE species  ff_mcmc_pair_kernel<NS, NOISE>
+//   ff_mc_spin_lanes   two lanes per walker, one per spin species (NU = ND = NS)    ff_mcmc_spin_kernel<NS, true>, ff_mcmc_spin_philox_kernel<NS, GROUND>
+//   ff_mc_pair_lanes   two lanes per walker splitting the particles of ONE species  ff_mcmc_pair_kernel<NS, NOISE, GROUND>
 // A layout provides  MS (coordinates per lane), M (per walker), w (ff_mc_head), load(row, dst), store(row, x), logprob(xs) and, for the
 // Philox-fed chains, draw(step, z, u); for the ratio chain also r2sum(xs) and polydet2(xs).  Everything is inlined and statically
 // indexed: nothing leaves the registers.  Same noise stream, same walkers, bit for bit, from every kernel of a shape.
@@ -78,6 +78,35 @@ FF_D ff_mc_head ff_mc_preamble(int64_t B, const int* __restrict__ tab_up, const 
   atomicMax(&s_md, md);
   __syncthreads();
   w.md = FF_UNIFORM(s_md);
+  w.wid = (uint64_t)(woff + w.b);
+  return w;
+}
+
+// A launch is GROUND when no per-walker state is given and both orbital tables are the list 0 .. NS-1 in order (closed shells: every
+// GSVMC model).  Decided on the device, once per kernel, from scalar loads of the tables -- neither the host nor the C ABI knows their
+// contents -- and the same for every wave of the launch.  (The pair kernel has one table: tab_b = tab_a.)
+template <int NS>
+FF_D bool ff_mc_is_ground(const int* __restrict__ tab_a, const int* __restrict__ tab_b, const int* __restrict__ wstate) {
+  int bad = wstate != nullptr ? 1 : 0;
+#pragma unroll
+  for (int j = 0; j < NS; j++) bad |= (tab_a[j] ^ j) | (tab_b[j] ^ j);
+  return FF_UNIFORM(bad) == 0;
+}
+// ff_mc_preamble of a ground launch: the degrees are the constants of ff_slater.h (the final log p, the reference's arithmetic, reads
+// them from o0 and md like every launch; the step loop of the ratio chain does not read them at all), so there is no table to decode,
+// no largest degree to agree on and no barrier.
+template <int LPW, int NS>
+FF_D ff_mc_head ff_mc_preamble_ground(int64_t B, int64_t woff, int* o0) {
+  static_assert(LPW == 2, "the two-lanes-per-walker layouts");
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  ff_mc_head w;
+  w.b = gid >> 1;
+  w.sub = (int)(gid & 1);
+  w.live = w.b < B;
+  if (!w.live) w.b = B - 1;
+#pragma unroll
+  for (int j = 0; j < NS; j++) { o0[j] = ff_ground_nx(j); o0[NS + j] = ff_ground_ny(j); }
+  w.md = ff_ground_md(NS);
   w.wid = (uint64_t)(woff + w.b);
   return w;
 }
@@ -229,7 +258,8 @@ struct ff_mc_one_lane {
 // Philox: the walker's blocks are dealt over its two lanes: lane 0 evaluates quads 0 .. mid, lane 1 the quads behind and the block of
 // the uniform; for odd NS the second half of the middle quad and the uniform change lanes by one DPP swap (two blocks per lane and
 // step at NS = 3 where every lane evaluated three).  Determinants up to 3 x 3 in closed form (no pivot search, no reciprocal).
-template <int NS>
+// GROUND: the launch is ground (ff_mc_is_ground) -- polydet2 with compile-time degrees; everything else is the same code.
+template <int NS, bool GROUND = false>
 struct ff_mc_spin_lanes {
   static constexpr int MS = 2 * NS, M = 2 * MS, n = 2 * NS;
   static constexpr bool ODD = (NS & 1) != 0;
@@ -257,7 +287,10 @@ struct ff_mc_spin_lanes {
     return R;
   }
   FF_D double polydet2(const double* x) const {      // (P_up P_dn)^2
-    const double P = ff_slater_polydet_reg<NS>(oo, oo + NS, x, w.md), PP = P * ff_swap1(P);
+    double P;
+    if constexpr (GROUND) P = ff_slater_polydet_ground<NS>(x);
+    else P = ff_slater_polydet_reg<NS>(oo, oo + NS, x, w.md);
+    const double PP = P * ff_swap1(P);
     return PP * PP;
   }
   // this spin's normals of one step (z[i]: coordinate sub * MS + i of the walker) and the walker's uniform of that step
@@ -303,7 +336,7 @@ struct ff_mc_spin_lanes {
 // hands through one DPP swap per entry, then both lanes run the same LU on the same matrix -- the same determinant bits, hence the
 // same accept decision, as one lane per walker.
 // slot s of a lane: particle pid(s) = 4 (s / 2) + 2 h + (s & 1)  (quad q = 2 (s / 2) + h); it exists if pid < NS
-template <int NS>
+template <int NS, bool GROUND = false>
 struct ff_mc_pair_lanes {
   static constexpr int M = 2 * NS, NQT = (NS + 1) / 2, NQL = (NQT + 1) / 2, NPL = 2 * NQL, MS = 2 * NPL;   // quads total / per lane, slots
   ff_mc_head w;
@@ -352,7 +385,10 @@ struct ff_mc_pair_lanes {
   FF_D double polydet2(const double* xs) const {
     double Dm[NPL][NS], Dfull[NS][NS];
 #pragma unroll
-    for (int sl = 0; sl < NPL; sl++) ff_poly_row_reg<NS>(oo, oo + NS, xs[2 * sl], xs[2 * sl + 1], w.md, Dm[sl]);
+    for (int sl = 0; sl < NPL; sl++) {
+      if constexpr (GROUND) ff_poly_row_ground<NS>(xs[2 * sl], xs[2 * sl + 1], Dm[sl]);
+      else ff_poly_row_reg<NS>(oo, oo + NS, xs[2 * sl], xs[2 * sl + 1], w.md, Dm[sl]);
+    }
     gather(Dm, Dfull);
     const double P = ff_det_reg<NS>(Dfull);
     return P * P;
@@ -386,32 +422,42 @@ ff_mcmc_spin_kernel(int64_t B, const int* __restrict__ tab_up, const int* __rest
                     int steps, double tau, const double* __restrict__ g0, const double* __restrict__ g,
                     const double* __restrict__ u, uint64_t seed, int64_t woff, double* __restrict__ x_out,
                     double* __restrict__ logp_out, uint8_t* __restrict__ accept, int* __restrict__ acc_count) {
-  static_assert(NOISE, "the Philox-fed chain of this layout is ff_mcmc_spin_philox_kernel<NS>");
+  static_assert(NOISE, "the Philox-fed chain of this layout is ff_mcmc_spin_philox_kernel<NS, GROUND>");
   ff_mc_spin_lanes<NS> L;
   L.w = ff_mc_preamble<2, NS, 0>(B, tab_up, tab_dn, wstate, woff, L.oo, nullptr);
   L.seed = seed;
   ff_mc_logp_chain<true>(L, B, steps, tau, g0, g, u, x_out, logp_out, accept, acc_count);
 }
 
-template <int NS>
+// The Philox-fed kernels come in two instantiations, GROUND and not, and the host launches BOTH: each derives the launch's flag
+// (ff_mc_is_ground) and the one it does not belong to returns at once -- a few scalar loads per wave.  One kernel with a uniform
+// branch would hold the registers of the larger path (156 at NS = 3) while it runs the smaller one (96).
+template <int NS, bool GROUND>
 __global__ void __launch_bounds__(128)
 ff_mcmc_spin_philox_kernel(int64_t B, const int* __restrict__ tab_up, const int* __restrict__ tab_dn, const int* __restrict__ wstate,
                            int steps, double tau, const double* __restrict__ g0, uint64_t seed, int64_t woff,
                            double* __restrict__ x_out, double* __restrict__ logp_out, int* __restrict__ acc_count) {
-  ff_mc_spin_lanes<NS> L;
-  L.w = ff_mc_preamble<2, NS, 0>(B, tab_up, tab_dn, wstate, woff, L.oo, nullptr);
+  if (ff_mc_is_ground<NS>(tab_up, tab_dn, wstate) != GROUND) return;      // wave-uniform, and the same in every wave of the launch
+  ff_mc_spin_lanes<NS, GROUND> L;
+  if constexpr (GROUND) L.w = ff_mc_preamble_ground<2, NS>(B, woff, L.oo);
+  else L.w = ff_mc_preamble<2, NS, 0>(B, tab_up, tab_dn, wstate, woff, L.oo, nullptr);     // excited orbitals, per-walker states, one spin ground only
   L.seed = seed;
   ff_mc_ratio_chain(L, steps, tau, g0, x_out, logp_out, acc_count);
 }
 
-template <int NS, bool NOISE>
+template <int NS, bool NOISE, bool GROUND = false>
 __global__ void __launch_bounds__(128)
 ff_mcmc_pair_kernel(int64_t B, const int* __restrict__ tab_up, const int* __restrict__ wstate, int steps, double tau,
                     const double* __restrict__ g0, const double* __restrict__ g, const double* __restrict__ u, uint64_t seed,
                     int64_t woff, double* __restrict__ x_out, double* __restrict__ logp_out, uint8_t* __restrict__ accept,
                     int* __restrict__ acc_count) {
-  ff_mc_pair_lanes<NS> L;
-  L.w = ff_mc_preamble<2, NS, 0>(B, tab_up, tab_up, wstate, woff, L.oo, nullptr);
+  static_assert(!(NOISE && GROUND), "the noise-fed chain is the reference's arithmetic for every launch");
+  if constexpr (!NOISE) {
+    if (ff_mc_is_ground<NS>(tab_up, tab_up, wstate) != GROUND) return;
+  }
+  ff_mc_pair_lanes<NS, GROUND> L;
+  if constexpr (GROUND) L.w = ff_mc_preamble_ground<2, NS>(B, woff, L.oo);
+  else L.w = ff_mc_preamble<2, NS, 0>(B, tab_up, tab_up, wstate, woff, L.oo, nullptr);
   L.seed = seed;
   if constexpr (NOISE) ff_mc_logp_chain<true>(L, B, steps, tau, g0, g, u, x_out, logp_out, accept, acc_count);
   else ff_mc_ratio_chain(L, steps, tau, g0, x_out, logp_out, acc_count);

@@ -187,6 +187,24 @@ FF_D bool ff_table_fetch(const double* __restrict__ tab, double inv_h, double h,
   return true;
 }
 
+// The same fetch without a branch: the row index is clamped (row 0 for a radius off the table, NaN included) and the row is loaded
+// always; the caller carries the returned predicate and selects.  The row address is a 32-bit byte offset from the (scalar) table
+// base: the largest is 2 x FF_TAB_NMAX rows.
+template <int NH>
+FF_D bool ff_table_fetch_always(const double* __restrict__ tab, double inv_h, double h, int t, double r, double* T, double& dr) {
+  static_assert((uint64_t)(FF_TAB_HDR + 2 * (uint64_t)FF_TAB_NMAX * FF_TAB_ROW) * 8 < (1ull << 31), "32-bit row offsets");
+  const bool ok = r < FF_TAB_RMAX;
+  const double jf = rint(r * inv_h);
+  dr = fma(-jf, h, r);
+  const int j = (int)(ok ? jf : 0.0);
+  const uint32_t off = (uint32_t)(FF_TAB_HDR + (t * FF_TAB_NMAX + j) * FF_TAB_ROW) * 8u;
+  const double* __restrict__ row = (const double*)((const char*)tab + off);
+  constexpr int NT = NH + 5 < FF_TAB_ROW ? NH + 5 : FF_TAB_ROW;
+#pragma unroll
+  for (int e = 0; e < NT; e++) T[e] = row[e];
+  return ok;
+}
+
 template <int NH>
 FF_D void ff_table_eval(const double* T, double dr, double* hd) {
   constexpr int NT = NH + 5 < FF_TAB_ROW ? NH + 5 : FF_TAB_ROW;

@@ -13,8 +13,8 @@ FF_D ff_u4 ff_philox(uint64_t key, uint64_t c01, uint32_t c2, uint32_t c3) {
 #pragma unroll
   for (int r = 0; r < 10; r++) {
     uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
-    uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    uint32_t n0 = ff_xor3((uint32_t)(p1 >> 32), c1, k0), n1 = (uint32_t)p1;
+    uint32_t n2 = ff_xor3((uint32_t)(p0 >> 32), c3, k1), n3 = (uint32_t)p0;
     c0 = n0; c1 = n1; c2 = n2; c3 = n3;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }

@@ -81,8 +81,10 @@ FF_D double ff_gauss2d_fast(double x, double y) { return ff_gauss_of_r2(x * x + 
 //   h_0 = 1, h_1 = sqrt(2) x, h_{m+1} = sqrt(2/(m+1)) x h_m - sqrt(m/(m+1)) h_{m-1}
 // (same polynomials as src/orbitals.py:66-73).  LU with partial pivoting; all indices static, row exchange by
 // predicated swaps, so the determinant stays in VGPRs.
-// (no table of all degrees + select: hipcc turns such a select chain into a runtime-indexed private array,
-//  i.e. scratch traffic on every Metropolis step; the short recurrence loop keeps two live values instead)
+// (no table of all degrees indexed by n: hipcc makes that a runtime-indexed private array, i.e. scratch traffic on every
+//  Metropolis step.  The short recurrence loop keeps two live values and picks the result by ONE SELECT PER DEGREE AND ORBITAL --
+//  a select chain all the same, 36 v_cndmask_b32 per step at 3 + 3 and 642 at 6 + 6, behind a constant-memory load per degree.
+//  Where the degrees are known at compile time -- the ground list, ff_poly_row_ground below -- there is neither.)
 __constant__ double FF_REC_A[7] = {1.4142135623730951, 1.0, 0.81649658092772603, 0.70710678118654752, 0.63245553203367588,
                                    0.57735026918962576, 0.53452248382484879};  // sqrt(2/(m+1)), m = 0..6
 __constant__ double FF_REC_B[7] = {0.0, 0.70710678118654752, 0.81649658092772603, 0.86602540378443865, 0.89442719099991588,
@@ -280,6 +282,54 @@ FF_D double ff_slater_polydet_reg(const int* nx, const int* ny, const double* x,
   double D[NS][NS];
 #pragma unroll
   for (int i = 0; i < NS; i++) ff_poly_row_reg<NS>(nx, ny, x[2 * i], x[2 * i + 1], md, D[i]);
+  return ff_det_reg<NS>(D);
+}
+
+// The same rows for the GROUND list of orbitals 0 .. NS-1 in order (closed shells: what every GSVMC model builds), with the degrees
+// as compile-time data: ff_ground_nx / ff_ground_ny restate ff_orb_decode as constexpr, the recurrence is unrolled over literal
+// coefficients as in ff_herm_one_d2 (no constant-memory load, no loop, no select), and an entry whose factor is h_0 = 1 is the other
+// factor itself instead of its product with 1.0.  The same three-term recurrence in the same order: the same bits as ff_poly_row_reg.
+constexpr int ff_ground_shell(int k) { int s = 0; while ((s + 1) * (s + 2) / 2 <= k) s++; return s; }
+constexpr int ff_ground_nx(int k) { return k - ff_ground_shell(k) * (ff_ground_shell(k) + 1) / 2; }
+constexpr int ff_ground_ny(int k) { return ff_ground_shell(k) - ff_ground_nx(k); }
+constexpr int ff_ground_md(int ns) { return ns > 0 ? ff_ground_shell(ns - 1) : 0; }      // largest degree among orbitals 0 .. ns-1
+// h[m] = h_m(x), m = 1 .. MD (h_0 = 1 is never stored)
+template <int MD>
+FF_D void ff_herm_lit(double x, double* h) {
+  constexpr double RA[7] = {1.4142135623730951, 1.0, 0.81649658092772603, 0.70710678118654752, 0.63245553203367588,
+                            0.57735026918962576, 0.53452248382484879};
+  constexpr double RB[7] = {0.0, 0.70710678118654752, 0.81649658092772603, 0.86602540378443865, 0.89442719099991588,
+                            0.91287092917527686, 0.92582009977255146};
+  static_assert(MD >= 0 && MD <= 7, "degrees of the 36 orbitals");
+  if constexpr (MD >= 1) h[1] = RA[0] * x;
+  if constexpr (MD >= 2) h[2] = fma(RA[1] * x, h[1], -RB[1]);                   // (-RB[1] * h_0)
+#pragma unroll
+  for (int m = 2; m < MD; m++) h[m + 1] = fma(RA[m] * x, h[m], -RB[m] * h[m - 1]);
+}
+template <int J, int NS>
+FF_D void ff_poly_row_ground_from(const double* hx, const double* hy, double* row) {
+  if constexpr (J < NS) {
+    constexpr int nx = ff_ground_nx(J), ny = ff_ground_ny(J);
+    if constexpr (nx == 0 && ny == 0) row[J] = 1.0;
+    else if constexpr (nx == 0) row[J] = hy[ny];
+    else if constexpr (ny == 0) row[J] = hx[nx];
+    else row[J] = hx[nx] * hy[ny];
+    ff_poly_row_ground_from<J + 1, NS>(hx, hy, row);
+  }
+}
+template <int NS>
+FF_D void ff_poly_row_ground(double x, double y, double* row) {
+  constexpr int MD = ff_ground_md(NS);
+  double hx[MD + 1], hy[MD + 1];
+  ff_herm_lit<MD>(x, hx);
+  ff_herm_lit<MD>(y, hy);
+  ff_poly_row_ground_from<0, NS>(hx, hy, row);
+}
+template <int NS>
+FF_D double ff_slater_polydet_ground(const double* x) {
+  double D[NS][NS];
+#pragma unroll
+  for (int i = 0; i < NS; i++) ff_poly_row_ground<NS>(x[2 * i], x[2 * i + 1], D[i]);
   return ff_det_reg<NS>(D);
 }
 

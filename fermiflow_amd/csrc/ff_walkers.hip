@@ -694,17 +694,23 @@ static void launch_mcmc(bool noise, void* stream, int64_t B, int nup, int ndn, c
     if (noise)
       FF_LAUNCH((ff_mcmc_spin_kernel<NU, true>), ff_grid(2 * B, 128), 128, stream, B, tu, td, ws, steps, tau, g0, g, u, seed, woff,
                 x_out, logp_out, accept, acc_count);
-    else
-      FF_LAUNCH((ff_mcmc_spin_philox_kernel<NU>), ff_grid(2 * B, 128), 128, stream, B, tu, td, ws, steps, tau, g0, seed, woff,
+    else {    // both instantiations: the kernels read the tables and the one the launch is not for returns at once (ff_mcmc.h)
+      FF_LAUNCH((ff_mcmc_spin_philox_kernel<NU, true>), ff_grid(2 * B, 128), 128, stream, B, tu, td, ws, steps, tau, g0, seed, woff,
                 x_out, logp_out, acc_count);
+      FF_LAUNCH((ff_mcmc_spin_philox_kernel<NU, false>), ff_grid(2 * B, 128), 128, stream, B, tu, td, ws, steps, tau, g0, seed, woff,
+                x_out, logp_out, acc_count);
+    }
   } else if constexpr (ND == 0 && NU >= 2 && NU <= 6) {
     // one spin species: two lanes per walker split the particles (ff_mcmc_pair_kernel)
     if (noise)
       FF_LAUNCH((ff_mcmc_pair_kernel<NU, true>), ff_grid(2 * B, 128), 128, stream, B, tu, ws, steps, tau, g0, g, u, seed, woff, x_out,
                 logp_out, accept, acc_count);
-    else
-      FF_LAUNCH((ff_mcmc_pair_kernel<NU, false>), ff_grid(2 * B, 128), 128, stream, B, tu, ws, steps, tau, g0, g, u, seed, woff, x_out,
+    else {
+      FF_LAUNCH((ff_mcmc_pair_kernel<NU, false, true>), ff_grid(2 * B, 128), 128, stream, B, tu, ws, steps, tau, g0, g, u, seed, woff, x_out,
                 logp_out, accept, acc_count);
+      FF_LAUNCH((ff_mcmc_pair_kernel<NU, false, false>), ff_grid(2 * B, 128), 128, stream, B, tu, ws, steps, tau, g0, g, u, seed, woff, x_out,
+                logp_out, accept, acc_count);
+    }
   } else {
     // one lane per walker: (1, 0) and (10, 0)
     if (noise)

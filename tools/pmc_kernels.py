@@ -12,7 +12,7 @@ import bench
 KERNELS = {"local-energy sensitivities + fused finish (two-wave matrix-core kernel)": "ff_eloc_mfma_kernel<6, 2, true, 2>",
            "local-energy sensitivities + finish (heavy route: the highest cost classes, one walker per wave)": "ff_wide_eloc_kernel<2, 1, true, double, true>",
            "theta-gradient adjoint (two waves per workgroup)": "ff_ode_adjtab_kernel<6, 2, 2>",
-           "Metropolis sampler (beside the adjoint)": "ff_mcmc_spin_philox_kernel<3>",
+           "Metropolis sampler (beside the adjoint)": "ff_mcmc_spin_philox_kernel<3, true>",
            "flow": "ff_ode_fwd_kernel<6, 2, 0, true>"}
 PASSES = (("FETCH_SIZE",), ("WRITE_SIZE",),
           ("SQ_WAVE_CYCLES", "SQ_ACTIVE_INST_VALU", "SQ_WAIT_ANY", "SQ_INSTS_VALU"),
