@@ -46,6 +46,9 @@ def build_parser():
                         help="adam: the reference's optimizer; sr: stochastic reconfiguration (fermiflow_amd/sr.py; not in the reference)")
     parser.add_argument("--sr_lr", type=float, default=0.05, help="learning rate of --optimizer sr")
     parser.add_argument("--sr_shift", type=float, default=1e-3, help="diagonal shift of the Fisher matrix of --optimizer sr")
+    parser.add_argument("--clip_eloc", type=float, default=None, metavar="K",
+                        help="robust estimator (not in the reference): drop failed walkers and clip the local energies to their median "
+                             "+- K mean absolute deviations before the gradient is formed; not with --optimizer sr")
     frames.add_arguments(parser)
     return parser
 
@@ -87,6 +90,10 @@ def main(argv=None):
     model = GSVMC(args.nup, args.ndown, orbitals, basedist, cnf, CoulombPairPotential(args.Z), sp_potential=HO())
     model.to(device=device)
     optimizer = make_optimizer(args, model)
+    if args.clip_eloc is not None:
+        if args.optimizer == "sr":
+            parser.error("--clip_eloc cannot be combined with --optimizer sr")
+        model.clip_eloc = args.clip_eloc
     if args.observe_out:
         model.observables = Observables(args.nup, args.ndown, dim=args.dim, rmax=args.observe_rmax, nbins=args.observe_bins, device=device)
     start_iter = 1
@@ -105,7 +112,8 @@ def main(argv=None):
         torch.cuda.synchronize()
         speed = (time.time() - start) * 100 / 3600
         if rank == 0:
-            print("iter: %03d" % i, "E:", model.E, "E_std:", model.E_std, "Instant speed (hours per 100 iters):", speed)
+            robust = ("n_valid:", model.n_valid, "n_clipped:", model.n_clipped) if model.clip_eloc is not None else ()
+            print("iter: %03d" % i, "E:", model.E, "E_std:", model.E_std, *robust, "Instant speed (hours per 100 iters):", speed)
             if args.save:
                 checkpoint.save(args.save, model, optimizer, i, device, observables=model.observables)
     if args.observe_out:

@@ -127,6 +127,15 @@ def _add_generic_potentials(r, x, extra):
     return r
 
 
+def _check_clip(k):
+    """clip_eloc: None, or a finite k > 0 as a float; anything else is a ValueError"""
+    if k is None:
+        return None
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or not (0.0 < float(k) < float("inf")):
+        raise ValueError(f"clip_eloc must be None or a finite number > 0, not {k!r}")
+    return float(k)
+
+
 # The adjoint opens with this factor x the largest step the walker's flow pass accepted (_adjoint_open; probed in round 5: 1.25 equal,
 # 1.4 worse over a 3000-iteration run)
 _ADJOINT_SCALE = 1.1
@@ -144,6 +153,10 @@ class _Sweep:
         self.observables = None
         # None, or an sr.SR (GSVMC only): every sweep then also leaves the Fisher matrix of the walkers' log-derivatives on it (_sweep)
         self.sr = None
+        # None, or a finite k > 0 (GSVMC only): the robust estimator -- failed walkers (a non-finite E_loc or logp) are dropped and the local
+        # energies are clipped to median +- k x (mean absolute deviation about it) before the gradient is formed (_robust_estimate;
+        # include/fermiflow_robust.h).  None: not a launch changes.
+        self.clip_eloc = None
         self.fast_backward = True    # _SweepScalar: `gradE.backward()` hands the gradient views to .grad without running the graph
         # ODE step-size warm start inside the sweep; FERMIFLOW_WARM_START=0 restores the cold start
         self.warm_start = os.environ.get("FERMIFLOW_WARM_START", "1") != "0"
@@ -324,10 +337,22 @@ class _Sweep:
         buf.copy_(both[:n].view_as(buf))
         return buf
 
+    @property
+    def clip_eloc(self):
+        return self.__dict__.get("_clip_eloc")
+
+    @clip_eloc.setter
+    def clip_eloc(self, k):
+        self.__dict__["_clip_eloc"] = _check_clip(k)
+
     def _scalar(self, key):
         return self._dev[key].item()
 
     def _std(self, key):
+        nv = self._dev.get("n_valid")
+        if nv is not None:      # a robust sweep: the spread of the n_v valid walkers (NaN for n_v <= 1, as for a batch of one)
+            var = torch.where(nv > 1.0, self._dev[key + "_ss"] / (nv - 1.0), torch.full_like(nv, float("nan")))
+            return var.clamp_min(0.0).sqrt().item()
         n = self._n_global
         # (the kernels clamp their centred sums of squares at zero; sums restored from an older checkpoint may carry a rounding-sized
         # negative one -- NaN stays NaN)
@@ -453,6 +478,50 @@ class GSVMC(_Sweep, torch.nn.Module):
     def E_std(self):
         return self._std("E")
 
+    # statistics of the robust estimator (model.clip_eloc set), read lazily from the device like E; Eloc_weights: the gradient weights u
+    # (B,), robust_stat: the ten doubles in the order of native.ROBUST_STAT -- both None unless the last sweep was a robust one
+    Eloc_weights = None
+    robust_stat = None
+
+    def _robust_scalar(self, key):
+        if key not in self._dev:
+            raise RuntimeError(f"{key} is a statistic of the robust estimator: set model.clip_eloc and run a sweep")
+        return self._scalar(key)
+
+    n_valid = property(lambda self: int(self._robust_scalar("n_valid")))
+    n_clipped = property(lambda self: int(self._robust_scalar("n_clipped")))
+    E_median = property(lambda self: self._robust_scalar("E_median"))
+    E_width = property(lambda self: self._robust_scalar("E_width"))
+
+    def _robust_estimate(self, Eloc, r, shift, batch):
+        """The robust estimator in place of ff_energy_estimate: (u, zero, value).  Statistics from the GLOBAL batch -- under data parallelism
+        one padded all-gather of the energies (invalid walkers marked NaN), after which every rank runs the selection on the same vector
+        and holds bit-identical statistics; only the one-double surrogate sum of the apply step is all-reduced, with the first-step
+        statistics riding along.  The apply step overwrites the z / glogp0 rows of failed walkers in place (0 x NaN would poison the
+        adjoint's sums)."""
+        logp = r["logp"]
+        if not D._active():
+            stat = native.energy_robust(Eloc, logp, self.clip_eloc, shift)
+            u, _ = native.energy_robust_apply(Eloc, logp, stat, batch, True, r["z"], r["glogp0"])
+            value = stat[9]
+        else:
+            _, world = D.world()
+            counts = [D.shard(batch, k, world)[1] for k in range(world)]
+            marked = torch.where(torch.isfinite(logp), Eloc, torch.full_like(Eloc, float("nan")))
+            g = D.all_gather_padded(marked, maxlen=max(counts))
+            # (the shard sizes are known on the host: the padding is cut off again, so that the sums run over exactly the walkers, in
+            # exactly the places, of a single-rank run)
+            stat = native.energy_robust(torch.cat([g[k, :counts[k]] for k in range(world)]), None, self.clip_eloc, shift)
+            u, s = native.energy_robust_apply(Eloc, logp, stat, batch, False, r["z"], r["glogp0"])
+            self._reduce_with_counts(s)
+            torch.div(s[0], stat[0], out=stat[9])      # (what the single rank's apply writes in its own launch)
+            value = stat[9]
+        for k, key in ((0, "n_valid"), (1, "E_median"), (2, "E_width"), (5, "E"), (6, "E_ss"), (8, "n_clipped")):
+            self._dev[key] = stat[k]
+        self._n_global = batch
+        self.robust_stat = stat      # the ten doubles in the order of native.ROBUST_STAT
+        return u, torch.zeros(1, dtype=Eloc.dtype, device=Eloc.device), value
+
     # -- pieces with the reference's names ---------------------------------------------------------
     def sample(self, sample_shape):
         z = self.basedist.sample(self.orbitals_up, self.orbitals_down, sample_shape)
@@ -568,6 +637,9 @@ class GSVMC(_Sweep, torch.nn.Module):
         return self._sweep(z.detach().contiguous(), int(batch if batch is not None else z.shape[0]), ev)
 
     def _sweep(self, z, batch, ev, prefetch=0):
+        if self.clip_eloc is not None and getattr(self, "sr", None) is not None:
+            raise NotImplementedError("GSVMC: clip_eloc and sr cannot be combined: the scores of failed walkers would poison the Fisher "
+                                      "matrix (fermiflow_amd/sr.py takes every walker)")
         self._first_sweep_sync()
         prof = self.profile
         with torch.no_grad():
@@ -583,13 +655,22 @@ class GSVMC(_Sweep, torch.nn.Module):
             # from E on the device (ff_cnf_adjoint_energy) -- nothing here waits for the host
             prev = self._dev.get("E")
             shift = prev.reshape(1) if prev is not None else torch.zeros(1, dtype=Eloc.dtype, device=Eloc.device)
-            if not D._active():
-                _, est = native.energy_estimate(Eloc, r["logp"], shift, batch)       # one launch: sums and finish (nothing to all-reduce)
+            if self.clip_eloc is not None:
+                # opt-in: failed walkers dropped, energies clipped about their median; the adjoint takes the weights u with a zero mean
+                seed_e, seed_mean, value = self._robust_estimate(Eloc, r, shift, batch)
             else:
-                sums, _ = native.energy_estimate(Eloc, r["logp"], shift, 0)
-                self._reduce_with_counts(sums)
-                est = native.energy_finish(sums, shift, batch)    # [E, sum (e - E)^2, mean(logp (e - E))]
-            self._dev["E"], self._dev["E_ss"], self._n_global = est[0], est[1], batch
+                if not D._active():
+                    _, est = native.energy_estimate(Eloc, r["logp"], shift, batch)       # one launch: sums and finish (nothing to all-reduce)
+                else:
+                    sums, _ = native.energy_estimate(Eloc, r["logp"], shift, 0)
+                    self._reduce_with_counts(sums)
+                    est = native.energy_finish(sums, shift, batch)    # [E, sum (e - E)^2, mean(logp (e - E))]
+                self._dev["E"], self._dev["E_ss"], self._n_global = est[0], est[1], batch
+                if "n_valid" in self._dev:      # (a robust sweep's statistics do not outlive it)
+                    for key in ("n_valid", "n_clipped", "E_median", "E_width"):
+                        self._dev.pop(key, None)
+                    self.Eloc_weights = self.robust_stat = None
+                seed_e, seed_mean, value = Eloc, est, est[2]
             self._mark(ev, "estimator")
             go, after = None, None
             if prefetch:      # the sampler's side stream is released by the library right behind the adjoint's main kernel (ff_ode.after_main_event)
@@ -599,7 +680,7 @@ class GSVMC(_Sweep, torch.nn.Module):
                 go.record(self._side)      # (creates the handle; the library re-records it on the main stream)
                 after = go
             adj = native.cnf_adjoint(net, r["z"], r["glogp0"], None, t0, t1, self.cnf.rtol, self.cnf.atol,
-                                     need_gx=False, energy=(Eloc, est, 1.0 / batch),   # (uniform cost: no schedule)
+                                     need_gx=False, energy=(seed_e, seed_mean, 1.0 / batch),   # (uniform cost: no schedule)
                                      after_main_event=after, want_stats=prof is not None, **self._adjoint_open(he))
             gp = adj[1]
             if prof is not None:
@@ -619,7 +700,9 @@ class GSVMC(_Sweep, torch.nn.Module):
         if prof is not None:
             prof.setdefault("events", []).append(ev)
         self.Eloc, self.x = Eloc, x
-        return _sweep_scalar(est[2], gp, params, self.fast_backward)
+        if seed_e is not Eloc:
+            self.Eloc_weights = seed_e      # u of the robust estimator (Eloc stays the raw energies)
+        return _sweep_scalar(value, gp, params, self.fast_backward)
 
 
 def draw_states_reference(logits, batch):
@@ -680,6 +763,17 @@ class BetaVMC(_Sweep, torch.nn.Module):
             raise NotImplementedError("BetaVMC takes stochastic reconfiguration as a BetaSR (fermiflow_amd/sr.py: per-state Fisher block "
                                       "and the categorical's block for the logits), not " + type(value).__name__)
         self.__dict__["_sr"] = value
+
+    # the robust estimator is GSVMC's: the per-state baseline and F need a definition of their own
+    @property
+    def clip_eloc(self):
+        return None
+
+    @clip_eloc.setter
+    def clip_eloc(self, k):
+        if k is not None:
+            raise NotImplementedError("BetaVMC has no robust estimator: clip_eloc is GSVMC's (the per-state baseline and F need a definition "
+                                      "of their own)")
 
     # How the many-body states of a batch are drawn: "order_statistics" (default; below) or "reference" -- the reference's own draw,
     # Categorical(logits).sample((batch,)) on torch's CPU generator, sorted (src/VMC.py:90-96): after the same torch.manual_seed the state

@@ -1,4 +1,5 @@
-"""The C ABI of include/fermiflow.h as ctypes sees it: its three structs and the signature of every function, declared once.
+"""The C ABI of include/fermiflow.h (and of include/fermiflow_robust.h: ROBUST_SIGNATURES) as ctypes sees it: its three structs and the
+signature of every function, declared once.
 fermiflow_amd._lib binds libfermiflow_hip.so to this table and tests/hostsim/simlib.py the host simulator's build of the same sources;
 tests/test_host_logic.py holds the table to the header, prototype by prototype.  Imports nothing but ctypes."""
 import ctypes as C
@@ -81,11 +82,19 @@ SIGNATURES = {      # name: (restype, argtypes), in the header's order; a new li
     "ff_beta_finish": (_I, (_P, _P, _P, _P, _I, _D, _Q, _P, _P, _P, _P)),
 }
 
+# include/fermiflow_robust.h, the second public header (the opt-in robust estimator), in its order
+ROBUST_SIGNATURES = {
+    "ff_energy_robust_workspace_bytes": (_Z, (_Q,)), "ff_energy_robust": (_I, (_P, _Q, _P, _P, _D, _P, _P, _P)),
+    "ff_energy_robust_apply": (_I, (_P, _Q, _I, _I, _P, _P, _P, _Q, _I, _P, _P, _P, _P, _P)),
+}
+ROBUST_NSTAT = 10      # FF_ROBUST_NSTAT: [n_v, m, a, lo, hi, E, E_ss, Ec, n_c, value]
+
 
 def bind(cdll):
-    """Set restype and argtypes of every function of SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the host simulator has
-    no ff_comm_*; an A/B build of an earlier commit may lack the newest) is skipped and fails where it is called, as any missing symbol."""
-    for name, (restype, argtypes) in SIGNATURES.items():
+    """Set restype and argtypes of every function of SIGNATURES and ROBUST_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
+    host simulator has no ff_comm_*; an A/B build of an earlier commit may lack the newest) is skipped and fails where it is called, as
+    any missing symbol."""
+    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES}.items():
         fn = getattr(cdll, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

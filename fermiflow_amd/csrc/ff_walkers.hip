@@ -678,6 +678,8 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
 
 // radial density and pair-distance histograms of the physical walkers (ff_observe_accumulate)
 #include "ff_observe.h"
+// the opt-in robust estimator: median by radix select, clipped local energies, gradient weights (ff_energy_robust, include/fermiflow_robust.h)
+#include "ff_robust.h"
 
 // =================================================================================================
 // C ABI
@@ -1291,6 +1293,45 @@ int ff_observe_accumulate(void* stream, int64_t B, int nup, int ndn, int d, cons
                   (double)nbins / rmax, nbins, ncopy, magic, b0 + nb == B ? B : (int64_t)0, (unsigned long long*)acc);
     FF_LAUNCH_CHECK();
   }
+  return FF_OK;
+}
+
+static inline int64_t ff_rob_segments(int64_t N) { return N > 0 ? (N + FF_ROB_SEG - 1) / FF_ROB_SEG : 1; }
+
+size_t ff_energy_robust_workspace_bytes(int64_t N) {
+  if (N < 0 || N >= FF_ROB_MAX_N) return 0;
+  return sizeof(double) * (FF_ROB_HDR + FF_ROB_PART * (size_t)ff_rob_segments(N));
+}
+
+int ff_energy_robust(void* stream, int64_t N, const double* e, const double* logp, double k, const double* shift_dev, double* stat,
+                     void* workspace) {
+  FF_CHECK(N > 0 && e && shift_dev && stat && workspace, FF_EINVAL, "ff_energy_robust: bad argument");
+  FF_CHECK(k > 0.0 && k <= 1.7976931348623157e308, FF_EINVAL, "ff_energy_robust: k must be positive and finite");
+  FF_CHECK(N < FF_ROB_MAX_N, FF_EUNSUPPORTED, "ff_energy_robust: N >= 2^31");
+  unsigned long long* ws = (unsigned long long*)workspace;
+  double* part = (double*)workspace + FF_ROB_HDR;
+  const unsigned nseg = (unsigned)ff_rob_segments(N);
+  for (int pass = 0; pass < FF_ROBUST_PASSES; pass++) {
+    FF_LAUNCH(ff_robust_select_kernel, ff_grid(N, FF_ROB_SEG, FF_ROB_MAX_GRID), FF_RBLOCK(FF_ROB_THREADS), stream, N, e, logp, pass, ws, stat);
+    FF_LAUNCH_CHECK();
+  }
+  FF_LAUNCH(ff_robust_moments_kernel, nseg, FF_RBLOCK(FF_ROB_THREADS), stream, N, e, logp, shift_dev, k, stat, part, ws + FF_ROB_W_TICKET);
+  FF_LAUNCH_CHECK();
+  FF_LAUNCH(ff_robust_clip_kernel, nseg, FF_RBLOCK(FF_ROB_THREADS), stream, N, e, logp, stat, part, ws + FF_ROB_W_TICKET);
+  FF_LAUNCH_CHECK();
+  return FF_OK;
+}
+
+int ff_energy_robust_apply(void* stream, int64_t B, int n, int d, const double* e, const double* logp, double* stat, int64_t n_global,
+                           int finish, double* u_out, double* z, double* glogp0, double* sum_out, void* workspace) {
+  FF_CHECK(B >= 0 && n_global > 0 && stat && sum_out && workspace && (B == 0 || (e && logp && u_out)) && (z != nullptr) == (glogp0 != nullptr),
+           FF_EINVAL, "ff_energy_robust_apply: bad argument");
+  FF_CHECK(B < FF_ROB_MAX_N, FF_EUNSUPPORTED, "ff_energy_robust_apply: B >= 2^31");
+  FF_CHECK(!z || (n >= 1 && d >= 1 && (int64_t)n * d <= FF_ROB_MAX_COORD), FF_EUNSUPPORTED, "ff_energy_robust_apply: n < 1, d < 1 or n d > 60");
+  unsigned long long* ws = (unsigned long long*)workspace;
+  FF_LAUNCH(ff_robust_apply_kernel, (unsigned)ff_rob_segments(B), FF_RBLOCK(FF_ROB_THREADS), stream, B, z ? n : 1, z ? d : 1, e, logp, stat,
+            (double)n_global, finish, u_out, z, glogp0, sum_out, (double*)workspace + FF_ROB_HDR, ws + FF_ROB_W_TICKET);
+  FF_LAUNCH_CHECK();
   return FF_OK;
 }
 

@@ -51,6 +51,30 @@ def broadcast_(t, src=0, force=False):
     return t
 
 
+def all_gather_padded(t, fill=float("nan"), maxlen=None):
+    """The 1-D shards `t` of all ranks as one (world, maxlen) tensor, every shard padded behind its end with `fill` to the longest
+    (the robust estimator gathers the local energies this way: a NaN energy is an invalid walker, so the padding needs no mask).
+    maxlen: the longest shard, where the caller knows it (VMC does, from shard()); None asks the ranks -- one more collective and a
+    host round trip.  A single rank gets its tensor back as (1, len) without a collective."""
+    t = t.reshape(-1)
+    if not _active():
+        return t.reshape(1, -1)
+    gloo = dist.get_backend() == "gloo"
+    if maxlen is None:
+        n = torch.tensor([t.numel()], dtype=torch.int64, device="cpu" if gloo else t.device)
+        dist.all_reduce(n, op=dist.ReduceOp.MAX)
+        maxlen = int(n.item())
+    if t.numel() > maxlen:
+        raise ValueError(f"all_gather_padded: a shard of {t.numel()} elements, maxlen {maxlen}")
+    mine = torch.full((int(maxlen),), fill, dtype=t.dtype, device=t.device)
+    mine[:t.numel()] = t
+    via_host = t.is_cuda and gloo      # test set-up: several ranks sharing one GPU over gloo
+    src = mine.cpu() if via_host else mine
+    out = torch.empty((dist.get_world_size(), int(maxlen)), dtype=t.dtype, device=src.device)
+    dist.all_gather(list(out.unbind(0)), src)
+    return out.to(t.device) if via_host else out
+
+
 def sync_parameters(module):
     """Every rank takes rank 0's parameters and buffers (one flat broadcast).  The estimators call this once, on their
     first sweep: ranks that built their model from differently seeded generators (e.g. BetaVMC's random state logits,

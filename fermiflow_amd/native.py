@@ -487,6 +487,51 @@ def energy_finish(sums4, shift_dev, n_global):
     return out
 
 
+_ROB_WS = {}      # (device, stream, N) -> zero-initialised workspace of ff_energy_robust / _apply (tickets, selection state and histogram are
+                  # left at zero by every call)
+ROBUST_STAT = ("n_valid", "E_median", "E_width", "lo", "hi", "E", "E_ss", "E_clipped", "n_clipped", "value")      # stat, include/fermiflow_robust.h
+
+
+def energy_robust(e, logp, k, shift_dev):
+    """ff_energy_robust on a whole batch: stat (10 doubles, ROBUST_STAT; [9] is written by energy_robust_apply).  logp = None: a walker is
+    valid where e is finite (the gathered energies of a data-parallel run, invalid walkers marked NaN)."""
+    e = L.dev(e, name="e"); shift_dev = L.dev(shift_dev.reshape(1), name="shift_dev")
+    logp = L.dev(logp, name="logp") if logp is not None else None
+    k = float(k)
+    N = e.numel()
+    key, ws = _cached_ws(_ROB_WS, 64, torch.zeros, e.device, (N,), lambda: L.lib().ff_energy_robust_workspace_bytes(N))
+    stat = torch.empty(L.ROBUST_NSTAT, dtype=torch.float64, device=e.device)
+    try:
+        L.check(L.lib().ff_energy_robust(L.stream(), N, L.ptr(e), L.ptr(logp), k, L.ptr(shift_dev), L.ptr(stat), L.ptr(ws)), "ff_energy_robust")
+    except Exception:
+        _ROB_WS.pop(key, None)      # a call that did not run to its end may have left a ticket or the histogram non-zero: never reuse it
+        raise
+    return stat
+
+
+def energy_robust_apply(e, logp, stat, n_global, finish=True, z=None, glogp0=None):
+    """ff_energy_robust_apply on this rank's shard: (u, sum_out (1,)).  Overwrites IN PLACE the rows of invalid walkers in z / glogp0
+    (both or neither) with the documented finite configuration / zeros; finish: stat[9] = sum_out / n_v in the same launch (single rank)."""
+    e = L.dev(e, name="e"); logp = L.dev(logp, name="logp"); stat = L.dev(stat, name="stat")
+    B = e.numel()
+    n = d = 0
+    if z is not None:
+        z = L.dev(z, name="z"); glogp0 = L.dev(glogp0, name="glogp0")
+        if not (z.dim() == 3 and z.shape[0] == B and glogp0.shape == z.shape):
+            raise ValueError("energy_robust_apply: z and glogp0 must both be (B, n, d)")
+        n, d = z.shape[1], z.shape[2]
+    key, ws = _cached_ws(_ROB_WS, 64, torch.zeros, e.device, (B,), lambda: L.lib().ff_energy_robust_workspace_bytes(B))
+    u = torch.empty(B, dtype=torch.float64, device=e.device)
+    s = torch.empty(1, dtype=torch.float64, device=e.device)
+    try:
+        L.check(L.lib().ff_energy_robust_apply(L.stream(), B, n, d, L.ptr(e), L.ptr(logp), L.ptr(stat), int(n_global), int(bool(finish)), L.ptr(u),
+                                               L.ptr(z), L.ptr(glogp0), L.ptr(s), L.ptr(ws)), "ff_energy_robust_apply")
+    except Exception:
+        _ROB_WS.pop(key, None)
+        raise
+    return u, s
+
+
 def beta_buffer(nstates, device):
     """buffer of ff_beta_state_partials / ff_beta_finish: [0:2] moments of E_loc, [2:] partial per-state sums."""
     return torch.empty(L.lib().ff_beta_buffer_doubles(int(nstates)), dtype=torch.float64, device=device)
