@@ -10,7 +10,7 @@ import time
 
 import torch
 
-from . import HO2D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, BetaVMC, Observables, checkpoint, frames
+from . import HO2D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, BetaVMC, DensityMaps, Observables, checkpoint, frames
 from .sr import BetaSR
 from .utils import make_adam
 
@@ -83,9 +83,12 @@ def main(argv=None):
     optimizer = make_optimizer(args, model)
     if args.observe_out:
         model.observables = Observables(args.nup, args.ndown, dim=2, rmax=args.observe_rmax, nbins=args.observe_bins, device=device)
+    if args.maps_out:
+        model.density_maps = DensityMaps(args.nup, args.ndown, extent=args.maps_extent, nbins=args.maps_bins, device=device)
     start_iter = 1
     if args.resume:
-        start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None) + 1
+        start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None,
+                                     maps=model.density_maps if rank == 0 else None) + 1
     if rank == 0:
         print("beta = %.1f, nup = %d, ndown = %d, Z = %.1f" % (args.beta, args.nup, args.ndown, args.Z))
         print("deltaE = %.1f, total number of states = %d" % (args.deltaE, model.Nstates))
@@ -105,15 +108,19 @@ def main(argv=None):
                   "S:", model.S, "S_analytical:", model.S_analytical,
                   "Instant speed (hours per 100 iters):", speed)
             if args.save:
-                checkpoint.save(args.save, model, optimizer, i, device, observables=model.observables)
+                checkpoint.save(args.save, model, optimizer, i, device, observables=model.observables, maps=model.density_maps)
     if args.observe_out:
         model.observables.all_reduce_()
         if rank == 0:
             model.observables.save_npz(args.observe_out)
-    if args.frames_out:
+    if args.maps_out:
+        model.density_maps.all_reduce_()
+        if rank == 0:
+            model.density_maps.save_npz(args.maps_out)
+    if args.frames_out or args.frames_maps_out:
         zx = model._sample_on_root((args.frames_batch,), nframes=args.nframes)      # (every rank: the state list is broadcast)
         if rank == 0:
-            frames.save_npz(args.frames_out, zx[1], cnf.t_span, args.nup, args.ndown, 2)
+            frames.write(args, zx[1], cnf.t_span, args.nup, args.ndown, 2)
     if world > 1:
         torch.distributed.destroy_process_group()
 

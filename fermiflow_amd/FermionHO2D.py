@@ -14,7 +14,7 @@ import time
 
 import torch
 
-from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, Observables, checkpoint, frames, native
+from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, DensityMaps, Observables, checkpoint, frames, native
 from .sr import SR
 from .utils import make_adam
 
@@ -96,9 +96,12 @@ def main(argv=None):
         model.clip_eloc = args.clip_eloc
     if args.observe_out:
         model.observables = Observables(args.nup, args.ndown, dim=args.dim, rmax=args.observe_rmax, nbins=args.observe_bins, device=device)
+    if args.maps_out:
+        model.density_maps = DensityMaps(args.nup, args.ndown, extent=args.maps_extent, nbins=args.maps_bins, device=device)
     start_iter = 1
     if args.resume:
-        start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None) + 1
+        start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None,
+                                     maps=model.density_maps if rank == 0 else None) + 1
     if rank == 0:
         print("nup = %d, ndown = %d, Z = %.1f" % (args.nup, args.ndown, args.Z))
         print("batch = %d, iternum = %d." % (args.batch, args.iternum))
@@ -115,14 +118,18 @@ def main(argv=None):
             robust = ("n_valid:", model.n_valid, "n_clipped:", model.n_clipped) if model.clip_eloc is not None else ()
             print("iter: %03d" % i, "E:", model.E, "E_std:", model.E_std, *robust, "Instant speed (hours per 100 iters):", speed)
             if args.save:
-                checkpoint.save(args.save, model, optimizer, i, device, observables=model.observables)
+                checkpoint.save(args.save, model, optimizer, i, device, observables=model.observables, maps=model.density_maps)
     if args.observe_out:
         model.observables.all_reduce_()
         if rank == 0:
             model.observables.save_npz(args.observe_out)
-    if args.frames_out and rank == 0:
+    if args.maps_out:
+        model.density_maps.all_reduce_()
+        if rank == 0:
+            model.density_maps.save_npz(args.maps_out)
+    if (args.frames_out or args.frames_maps_out) and rank == 0:
         z = basedist.sample(model.orbitals_up, model.orbitals_down, (args.frames_batch,))
-        frames.save_npz(args.frames_out, cnf.generate(z, nframes=args.nframes), cnf.t_span, args.nup, args.ndown, args.dim)
+        frames.write(args, cnf.generate(z, nframes=args.nframes), cnf.t_span, args.nup, args.ndown, args.dim)
     if world > 1:
         torch.distributed.destroy_process_group()
 

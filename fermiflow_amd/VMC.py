@@ -151,6 +151,8 @@ class _Sweep:
         self.profile = None
         # None, or an observables.Observables: every sweep then adds its physical walkers to it (one launch right after the flow pass)
         self.observables = None
+        # None, or an observables.DensityMaps (d = 2): every sweep then adds its physical walkers to its maps (one more launch, next to it)
+        self.density_maps = None
         # None, or an sr.SR (GSVMC only): every sweep then also leaves the Fisher matrix of the walkers' log-derivatives on it (_sweep)
         self.sr = None
         # None, or a finite k > 0 (GSVMC only): the robust estimator -- failed walkers (a non-finite E_loc or logp) are dropped and the local
@@ -255,6 +257,8 @@ class _Sweep:
                                 walker_h_init=hprev, walker_h_scale=0.75, walker_h_out=hg, walker_h_uniform=uniform)
         if self.observables is not None:
             self.observables.accumulate(x)
+        if self.density_maps is not None:
+            self.density_maps.accumulate(x)
         self.walker_cost = cost          # the flow pass's cost class per walker (diagnostics and tests; ff_ode.walker_cost)
         hs = None
         if warm and not per_walker_h and self.adaptive_h:

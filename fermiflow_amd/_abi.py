@@ -1,4 +1,4 @@
-"""The C ABI of include/fermiflow.h (and of include/fermiflow_robust.h: ROBUST_SIGNATURES) as ctypes sees it: its three structs and the
+"""The C ABI of include/fermiflow.h (and of include/fermiflow_robust.h: ROBUST_SIGNATURES; include/fermiflow_maps.h: MAPS_SIGNATURES) as ctypes sees it: its three structs and the
 signature of every function, declared once.
 fermiflow_amd._lib binds libfermiflow_hip.so to this table and tests/hostsim/simlib.py the host simulator's build of the same sources;
 tests/test_host_logic.py holds the table to the header, prototype by prototype.  Imports nothing but ctypes."""
@@ -89,12 +89,18 @@ ROBUST_SIGNATURES = {
 }
 ROBUST_NSTAT = 10      # FF_ROBUST_NSTAT: [n_v, m, a, lo, hi, E, E_ss, Ec, n_c, value]
 
+# include/fermiflow_maps.h, the third public header (density maps), in its order
+MAPS_SIGNATURES = {
+    "ff_maps_buffer_bytes": (_Z, (_I,)), "ff_maps_accumulate": (_I, (_P, _Q, _I, _I, _P, _D, _I, _P)),
+}
+MAPS_PLANES, MAPS_MAX_BINS = 6, 128      # FF_MAPS_PLANES, FF_MAPS_MAX_BINS
+
 
 def bind(cdll):
-    """Set restype and argtypes of every function of SIGNATURES and ROBUST_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
+    """Set restype and argtypes of every function of SIGNATURES, ROBUST_SIGNATURES and MAPS_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
     host simulator has no ff_comm_*; an A/B build of an earlier commit may lack the newest) is skipped and fails where it is called, as
     any missing symbol."""
-    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES, **MAPS_SIGNATURES}.items():
         fn = getattr(cdll, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

@@ -14,17 +14,20 @@ unchanged), not bit for bit.
 to continue its averages: save() stores the writing rank's own counts (its state_dict), load() restores them into the accumulator
 it is given.  The drivers pass the accumulator on rank 0 only, so the counts of rank 0's shard continue; the other ranks of a
 multi-rank run start theirs again at the resume (their earlier blocks are in no checkpoint), which leaves every average unbiased
-and built from fewer blocks.  A checkpoint without observables leaves the accumulator as it is."""
+and built from fewer blocks.  A checkpoint without observables leaves the accumulator as it is.
+`maps` (a DensityMaps accumulator, the drivers' --maps_out) is handled exactly as `observables` is."""
 import os
 
 import torch
 
 
-def save(path, model, optimizer, it, device=None, observables=None):
+def save(path, model, optimizer, it, device=None, observables=None, maps=None):
     ck = {"model": model.state_dict(), "optimizer": optimizer.state_dict(), "iter": int(it),
           "rng_cpu": torch.get_rng_state(), "optimizer_kind": getattr(optimizer, "kind", "adam")}
     if observables is not None:
         ck["observables"] = observables.state_dict()
+    if maps is not None:
+        ck["maps"] = maps.state_dict()
     if device is not None and torch.device(device).type == "cuda":
         ck["rng_cuda"] = torch.cuda.get_rng_state(device)
     tmp = path + ".tmp"
@@ -32,7 +35,7 @@ def save(path, model, optimizer, it, device=None, observables=None):
     os.replace(tmp, path)          # a crash while writing never leaves a truncated checkpoint behind
 
 
-def load(path, model, optimizer, device=None, observables=None):
+def load(path, model, optimizer, device=None, observables=None, maps=None):
     """Restores model / optimizer / RNG state in place; returns the iteration the checkpoint was written after."""
     ck = torch.load(path, map_location=device, weights_only=True)      # tensors, dicts, ints only: nothing to unpickle
     kind = ck.get("optimizer_kind", "adam")      # (checkpoints without the key were written with Adam)
@@ -46,4 +49,6 @@ def load(path, model, optimizer, device=None, observables=None):
         torch.cuda.set_rng_state(ck["rng_cuda"].cpu(), device)
     if observables is not None and "observables" in ck:
         observables.load_state_dict(ck["observables"])
+    if maps is not None and "maps" in ck:
+        maps.load_state_dict(ck["maps"])
     return int(ck["iter"])

@@ -678,6 +678,8 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
 
 // radial density and pair-distance histograms of the physical walkers (ff_observe_accumulate)
 #include "ff_observe.h"
+// lab-frame density maps and rotating-frame pair densities of the physical walkers (ff_maps_accumulate, include/fermiflow_maps.h)
+#include "ff_maps.h"
 // the opt-in robust estimator: median by radix select, clipped local energies, gradient weights (ff_energy_robust, include/fermiflow_robust.h)
 #include "ff_robust.h"
 
@@ -1291,6 +1293,38 @@ int ff_observe_accumulate(void* stream, int64_t B, int nup, int ndn, int d, cons
     const unsigned grid = ff_grid((nb + FF_WAVE - 1) / FF_WAVE, nwave, ff_device_cus() * FF_OBS_GRID_PER_CU);
     FF_LAUNCH_LDS(ff_observe_kernel, grid, nwave * FF_WAVE, hist_bytes + nwave * wave_bytes, stream, nb, nup, n, d, x + b0 * M, rmax,
                   (double)nbins / rmax, nbins, ncopy, magic, b0 + nb == B ? B : (int64_t)0, (unsigned long long*)acc);
+    FF_LAUNCH_CHECK();
+  }
+  return FF_OK;
+}
+
+size_t ff_maps_buffer_bytes(int nbins) {
+  if (nbins < 1 || nbins > FF_MAPS_MAX_BINS) return 0;
+  return sizeof(unsigned long long) * (2 + (size_t)FF_MAPS_PLANES * FF_MAPS_SLOTS(nbins));
+}
+
+int ff_maps_accumulate(void* stream, int64_t B, int nup, int ndn, const double* x, double extent, int nbins, void* acc) {
+  FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && (int64_t)nup + ndn >= 1 && acc && (x || B == 0), FF_EINVAL, "ff_maps: bad argument");
+  FF_CHECK(nbins >= 1, FF_EINVAL, "ff_maps: nbins < 1");
+  FF_CHECK(extent > 0.0 && extent <= 1.7976931348623157e308, FF_EINVAL, "ff_maps: extent must be positive and finite");
+  FF_CHECK(nbins <= FF_MAPS_MAX_BINS, FF_EUNSUPPORTED, "ff_maps: nbins > 128");
+  FF_CHECK((int64_t)nup + ndn <= FF_MAX_N, FF_EUNSUPPORTED, "ff_maps: n > 24");
+  if (B == 0) return FF_OK;
+  const int n = nup + ndn, P = FF_MAPS_SLOTS(nbins);
+  const int samples[FF_MAPS_PLANES] = {nup, ndn, nup * (nup - 1), nup * ndn, ndn * nup, ndn * (ndn - 1)};
+  unsigned planes = 0u;                 // the planes that have samples, three bits each
+  int nact = 0;
+  for (int p = 0; p < FF_MAPS_PLANES; p++)
+    if (samples[p] > 0) planes |= (unsigned)p << (3 * nact++);
+  const int nbands = (P + FF_MAPS_BAND_WORDS - 1) / FF_MAPS_BAND_WORDS, W = (P + nbands - 1) / nbands, per = nact * nbands;
+  const size_t lds_bytes = sizeof(double) * (size_t)((W + 1) / 2);
+  for (int64_t b0 = 0; b0 < B; b0 += FF_MAPS_MAX_LAUNCH) {      // one launch up to 2^22 walkers; the last launch closes the call
+    const int64_t nb = B - b0 < FF_MAPS_MAX_LAUNCH ? B - b0 : FF_MAPS_MAX_LAUNCH;
+    const int nwave = nb >= 4 * FF_WAVE ? 4 : (int)((nb + FF_WAVE - 1) / FF_WAVE);
+    const int64_t ntiles = (nb + nwave * FF_WAVE - 1) / (nwave * FF_WAVE), cap = ff_device_cus() * FF_MAPS_GRID_PER_CU / per;
+    const unsigned nslice = ff_grid(ntiles, FF_MAPS_MIN_TILES, cap > 1 ? cap : 1);
+    FF_LAUNCH_LDS(ff_maps_kernel, nslice * (unsigned)per, nwave * FF_WAVE, lds_bytes, stream, nb, nup, n, x + b0 * 2 * n, extent,
+                  (double)nbins / (2.0 * extent), nbins, planes, nact, nbands, W, b0 + nb == B ? B : (int64_t)0, (unsigned long long*)acc);
     FF_LAUNCH_CHECK();
   }
   return FF_OK;

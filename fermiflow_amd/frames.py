@@ -1,5 +1,9 @@
 """Flow trajectories for the drivers: `--frames_out FILE.npz` writes the frames of CNF.generate(z, nframes) (src/flow.py:45-48)
-for a fresh batch of base walkers after the last iteration -- particles moving from the free-fermion base to the interacting state."""
+for a fresh batch of base walkers after the last iteration -- particles moving from the free-fermion base to the interacting state.
+`--frames_maps_out FILE.npz` writes the density maps (observables.DensityMaps) of the same walkers, one set per frame, binned on the
+device: without --frames_out no trajectory goes to the host.  The flags of the run's own maps (`--maps_out`) are declared here too."""
+import math
+
 import numpy as np
 import torch
 
@@ -9,13 +13,26 @@ def add_arguments(parser):
                         help=".npz file for the flow trajectory of a fresh batch of base walkers, written after the last iteration")
     parser.add_argument("--nframes", type=int, default=50, help="number of frames of --frames_out (torch.linspace(t0, t1, nframes))")
     parser.add_argument("--frames_batch", type=int, default=1024, help="number of walkers of --frames_out")
+    parser.add_argument("--maps_out", type=str, default=None,
+                        help=".npz file for the density maps rho(x, y) and the rotating-frame pair densities averaged over the run's iterations")
+    parser.add_argument("--maps_extent", type=float, default=6.0, help="the maps cover the square [-extent, extent)^2")
+    parser.add_argument("--maps_bins", type=int, default=128, help="cells per axis of the maps (at most 128)")
+    parser.add_argument("--frames_maps_out", type=str, default=None,
+                        help=".npz file for the density maps of every frame of the --frames_out trajectory's walkers (also without --frames_out)")
 
 
 def check_arguments(parser, args):
-    if args.frames_out and args.nframes < 1:
+    if (args.frames_out or args.frames_maps_out) and args.nframes < 1:
         parser.error("--nframes must be at least 1")
-    if args.frames_out and args.frames_batch < 1:
+    if (args.frames_out or args.frames_maps_out) and args.frames_batch < 1:
         parser.error("--frames_batch must be at least 1")
+    if args.maps_out or args.frames_maps_out:
+        if getattr(args, "dim", 2) != 2:
+            parser.error("--maps_out and --frames_maps_out are two-dimensional maps: not with --dim 3")
+        if not 1 <= args.maps_bins <= 128:
+            parser.error("--maps_bins must be between 1 and 128")
+        if not (args.maps_extent > 0.0 and math.isfinite(args.maps_extent)):
+            parser.error("--maps_extent must be positive and finite")
 
 
 def save_npz(path, frames, t_span, nup, ndown, dim):
@@ -23,3 +40,14 @@ def save_npz(path, frames, t_span, nup, ndown, dim):
     t = torch.linspace(float(t_span[0]), float(t_span[1]), frames.shape[0], dtype=torch.float64)
     with open(path, "wb") as f:      # (an open file: numpy appends no suffix of its own to the name)
         np.savez(f, t=t.numpy(), frames=frames.detach().cpu().numpy(), nup=np.int64(nup), ndown=np.int64(ndown), dim=np.int64(dim))
+
+
+def write(args, frames, t_span, nup, ndown, dim):
+    """What the drivers do with the trajectory frames (K, B, n, dim) on the device: --frames_out and / or --frames_maps_out."""
+    if args.frames_out:
+        save_npz(args.frames_out, frames, t_span, nup, ndown, dim)
+    if args.frames_maps_out:
+        from .observables import DensityMaps
+        maps = DensityMaps(nup, ndown, extent=args.maps_extent, nbins=args.maps_bins, nframes=frames.shape[0], device=frames.device)
+        maps.accumulate_frames(frames)
+        maps.save_npz(args.frames_maps_out)
