@@ -85,6 +85,7 @@ def main(argv=None):
         model.observables = Observables(args.nup, args.ndown, dim=2, rmax=args.observe_rmax, nbins=args.observe_bins, device=device)
     if args.maps_out:
         model.density_maps = DensityMaps(args.nup, args.ndown, extent=args.maps_extent, nbins=args.maps_bins, device=device)
+    frames.attach_obdm(args, model, args.nup, args.ndown, device)
     start_iter = 1
     if args.resume:
         start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None,
@@ -117,6 +118,7 @@ def main(argv=None):
         model.density_maps.all_reduce_()
         if rank == 0:
             model.density_maps.save_npz(args.maps_out)
+    frames.write_obdm(args, model, rank)
     if args.frames_out or args.frames_maps_out:
         zx = model._sample_on_root((args.frames_batch,), nframes=args.nframes)      # (every rank: the state list is broadcast)
         if rank == 0:

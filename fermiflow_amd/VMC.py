@@ -153,6 +153,11 @@ class _Sweep:
         self.observables = None
         # None, or an observables.DensityMaps (d = 2): every sweep then adds its physical walkers to its maps (one more launch, next to it)
         self.density_maps = None
+        # None, or an observables.OneBodyDensityMatrix (d = 2): every `every`-th sweep then measures the one-body density matrix of its
+        # walkers right after the local-energy pass (the backward flows of the moved walkers: OneBodyDensityMatrix.measure).  A setting,
+        # not sweep state; None: not a launch changes
+        self._sweep_dim = dim
+        self.obdm = None
         # None, or an sr.SR (GSVMC only): every sweep then also leaves the Fisher matrix of the walkers' log-derivatives on it (_sweep)
         self.sr = None
         # None, or a finite k > 0 (GSVMC only): the robust estimator -- failed walkers (a non-finite E_loc or logp) are dropped and the local
@@ -306,6 +311,8 @@ class _Sweep:
                 self._h_counts_local = native.scale_counts(cost, hs, he, interval=t1 - t0)
             else:
                 self._h_prev = (cost, hs, he)
+        if self.obdm is not None:
+            self.obdm.on_sweep(net, tu, td, x, r["z"], r["logp"], (t0, t1), self.cnf.rtol, self.cnf.atol, walker_state)
         _add_generic_potentials(r, x, extra)
         self._mark(ev, "eloc")
         if prof is not None:
@@ -348,6 +355,16 @@ class _Sweep:
     @clip_eloc.setter
     def clip_eloc(self, k):
         self.__dict__["_clip_eloc"] = _check_clip(k)
+
+    @property
+    def obdm(self):
+        return self.__dict__.get("_obdm")
+
+    @obdm.setter
+    def obdm(self, obj):
+        if obj is not None and self.__dict__.get("_sweep_dim", 2) != 2:
+            raise NotImplementedError("obdm: the one-body density matrix is measured in the two-dimensional oscillator basis, this model has dim = 3")
+        self.__dict__["_obdm"] = obj
 
     def _scalar(self, key):
         return self._dev[key].item()

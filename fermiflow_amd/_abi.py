@@ -1,4 +1,5 @@
-"""The C ABI of include/fermiflow.h (and of include/fermiflow_robust.h: ROBUST_SIGNATURES; include/fermiflow_maps.h: MAPS_SIGNATURES) as ctypes sees it: its three structs and the
+"""The C ABI of include/fermiflow.h (and of include/fermiflow_robust.h: ROBUST_SIGNATURES; include/fermiflow_maps.h: MAPS_SIGNATURES;
+include/fermiflow_obdm.h: OBDM_SIGNATURES) as ctypes sees it: its three structs and the
 signature of every function, declared once.
 fermiflow_amd._lib binds libfermiflow_hip.so to this table and tests/hostsim/simlib.py the host simulator's build of the same sources;
 tests/test_host_logic.py holds the table to the header, prototype by prototype.  Imports nothing but ctypes."""
@@ -95,12 +96,20 @@ MAPS_SIGNATURES = {
 }
 MAPS_PLANES, MAPS_MAX_BINS = 6, 128      # FF_MAPS_PLANES, FF_MAPS_MAX_BINS
 
+# include/fermiflow_obdm.h, the fourth public header (one-body density matrix, determinant signs), in its order
+OBDM_SIGNATURES = {
+    "ff_slater_sign": (_I, (_P, _Q, _I, _I, _P, _P, _P, _P, _P)),
+    "ff_obdm_buffer_bytes": (_Z, (_I,)), "ff_obdm_workspace_bytes": (_Z, (_Q, _I)),
+    "ff_obdm_accumulate": (_I, (_P, _Q, _I, _I, _P, _P, _P, _P, _P, _P, _D, _I, _P, _P)),
+}
+OBDM_MAX_SHELLS, OBDM_CHUNK, OBDM_HEAD = 8, 256, 5      # FF_OBDM_MAX_SHELLS, FF_OBDM_CHUNK, FF_OBDM_HEAD
+
 
 def bind(cdll):
-    """Set restype and argtypes of every function of SIGNATURES, ROBUST_SIGNATURES and MAPS_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
+    """Set restype and argtypes of every function of SIGNATURES, ROBUST_SIGNATURES, MAPS_SIGNATURES and OBDM_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
     host simulator has no ff_comm_*; an A/B build of an earlier commit may lack the newest) is skipped and fails where it is called, as
     any missing symbol."""
-    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES, **MAPS_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES, **MAPS_SIGNATURES, **OBDM_SIGNATURES}.items():
         fn = getattr(cdll, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

@@ -191,9 +191,10 @@ FF_D double ff_inv_small(const double (&A)[NS][NS], double (&Ai)[NS][NS]) {
 // e2 != null: the running product is kept as a mantissa in [1/2, 1) and the power of two goes to *e2, |det| = result * 2^*e2
 // (the product of NS pivots that carry their rows' Gaussians leaves the double range in the tail of the density).  Scaling by
 // powers of two is exact, so the mantissa has the bits of the plain product wherever that product is a normal number.
+// sgn != null: *sgn = sign(det D) = (-1)^exchanges prod sgn(pivot), in {-1, 0 (of either sign), +1}, NaN if a pivot is (ff_slater_sign).
 template <int NS>
-FF_D double ff_lu_absdet_reg(double (&D)[NS][NS], int* e2 = nullptr) {
-  double prod = 1.0;
+FF_D double ff_lu_absdet_reg(double (&D)[NS][NS], int* e2 = nullptr, double* sgn = nullptr) {
+  double prod = 1.0, sg = 1.0;
   int ex = 0;
 #pragma unroll
   for (int c = 0; c < NS; c++) {
@@ -217,6 +218,7 @@ FF_D double ff_lu_absdet_reg(double (&D)[NS][NS], int* e2 = nullptr) {
     double piv = D[c][c];
     prod *= fabs(piv);
     if (e2) { int e; prod = frexp(prod, &e); ex += e; }
+    if (sgn) sg *= (p != c ? -1.0 : 1.0) * (piv > 0.0 ? 1.0 : (piv < 0.0 ? -1.0 : (piv == 0.0 ? 0.0 : piv)));
     const double ip = piv != 0.0 ? 1.0 / piv : 0.0, one = piv != 0.0 ? 1.0 : 0.0;
 #pragma unroll
     for (int r = c + 1; r < NS; r++) {
@@ -227,6 +229,7 @@ FF_D double ff_lu_absdet_reg(double (&D)[NS][NS], int* e2 = nullptr) {
     }
   }
   if (e2) *e2 = ex;
+  if (sgn) *sgn = sg;
   return prod;
 }
 // log|det D|: one log per determinant, of mantissa * 2^e.  Where |det| is a normal double the log is taken of |det| itself (the

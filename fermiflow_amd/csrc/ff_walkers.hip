@@ -680,6 +680,8 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
 #include "ff_observe.h"
 // lab-frame density maps and rotating-frame pair densities of the physical walkers (ff_maps_accumulate, include/fermiflow_maps.h)
 #include "ff_maps.h"
+// one-body density matrix in the oscillator basis and the sign of the Slater determinants (include/fermiflow_obdm.h)
+#include "ff_obdm.h"
 // the opt-in robust estimator: median by radix select, clipped local energies, gradient weights (ff_energy_robust, include/fermiflow_robust.h)
 #include "ff_robust.h"
 
@@ -1327,6 +1329,55 @@ int ff_maps_accumulate(void* stream, int64_t B, int nup, int ndn, const double* 
                   (double)nbins / (2.0 * extent), nbins, planes, nact, nbands, W, b0 + nb == B ? B : (int64_t)0, (unsigned long long*)acc);
     FF_LAUNCH_CHECK();
   }
+  return FF_OK;
+}
+
+int ff_slater_sign(void* stream, int64_t B, int nup, int ndn, const int32_t* tab_up, const int32_t* tab_dn, const int32_t* walker_state,
+                   const double* z, double* sign_out) {
+  FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && (int64_t)nup + ndn >= 1 && (B == 0 || (z && sign_out)), FF_EINVAL, "ff_obdm: bad argument");
+  FF_CHECK((int64_t)nup + ndn <= FF_MAX_N && B < ((int64_t)1 << 31), FF_EUNSUPPORTED, "ff_obdm: n > 24 or B >= 2^31");
+  if (const int st = ff_check_spins("ff_obdm", nup, ndn, tab_up, tab_dn)) return st;
+  if (B == 0) return FF_OK;
+#define FF_SGN(NS_) case NS_: FF_LAUNCH((ff_slater_sign_kernel<NS_>), ff_grid(B, FF_WAVE), FF_WAVE, stream, B, nup, ndn, tab_up, tab_dn, walker_state, z, sign_out); break;
+  switch (nup > ndn ? nup : ndn) {
+    FF_SGN(1) FF_SGN(2) FF_SGN(3) FF_SGN(4) FF_SGN(5) FF_SGN(6) FF_SGN(7) FF_SGN(8) FF_SGN(9) FF_SGN(10) FF_SGN(11) FF_SGN(12)
+    default: break;
+  }
+#undef FF_SGN
+  FF_LAUNCH_CHECK();
+  return FF_OK;
+}
+
+size_t ff_obdm_buffer_bytes(int nshells) {
+  if (nshells < 1 || nshells > FF_OBDM_MAX_SHELLS) return 0;
+  return sizeof(double) * (FF_OBDM_HEAD + 4 * (size_t)FF_OBDM_NB(nshells) * FF_OBDM_NB(nshells));
+}
+
+size_t ff_obdm_workspace_bytes(int64_t B, int nshells) {
+  if (nshells < 1 || nshells > FF_OBDM_MAX_SHELLS || B < 0 || B >= ((int64_t)1 << 31)) return 0;
+  const size_t nchunks = B > 0 ? (size_t)((B + FF_OBDM_CHUNK - 1) / FF_OBDM_CHUNK) : 1;
+  return sizeof(double) * nchunks * 2 * (size_t)FF_OBDM_NB(nshells) * FF_OBDM_NB(nshells);
+}
+
+int ff_obdm_accumulate(void* stream, int64_t B, int nup, int ndn, const double* x, const double* rprime, const double* logp,
+                       const double* sign, const double* logp_moved, const double* sign_moved, double sigma, int nshells, void* acc,
+                       void* workspace) {
+  FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && (int64_t)nup + ndn >= 1 && acc &&
+           (B == 0 || (x && rprime && logp && sign && logp_moved && sign_moved && workspace)), FF_EINVAL, "ff_obdm: bad argument");
+  FF_CHECK(nshells >= 1, FF_EINVAL, "ff_obdm: nshells < 1");
+  FF_CHECK(sigma > 0.0 && sigma <= 1.7976931348623157e308, FF_EINVAL, "ff_obdm: sigma must be positive and finite");
+  FF_CHECK(nshells <= FF_OBDM_MAX_SHELLS, FF_EUNSUPPORTED, "ff_obdm: nshells > 8");
+  FF_CHECK((int64_t)nup + ndn <= FF_MAX_N, FF_EUNSUPPORTED, "ff_obdm: n > 24");
+  if (const int st = ff_check_det_size("ff_obdm", nup, ndn)) return st;
+  FF_CHECK(B < ((int64_t)1 << 31), FF_EUNSUPPORTED, "ff_obdm: B >= 2^31");
+  if (B == 0) return FF_OK;
+  const int nb = FF_OBDM_NB(nshells), lgslab = nb <= 10 ? 7 : (nb <= 21 ? 6 : 5);      // a slab's vectors: at most 44 KB
+  const size_t slab_words = 2 * ((size_t)1 << lgslab) * (2 * nb + 1), fold_words = 2 * (size_t)nb * nb;
+  const unsigned grid = ff_grid((B + FF_OBDM_CHUNK - 1) / FF_OBDM_CHUNK, 1, ff_device_cus() * FF_OBDM_GRID_PER_CU);
+  FF_LAUNCH_LDS(ff_obdm_kernel, grid, FF_OBDM_THREADS, sizeof(double) * (slab_words > fold_words ? slab_words : fold_words), stream, B, nup,
+                nup + ndn, x, rprime, logp, sign, logp_moved, sign_moved, 2.0 * sigma * sigma, 6.283185307179586 * sigma * sigma, nshells,
+                lgslab, (unsigned long long*)acc, (double*)workspace);
+  FF_LAUNCH_CHECK();
   return FF_OK;
 }
 

@@ -1,7 +1,8 @@
 """Flow trajectories for the drivers: `--frames_out FILE.npz` writes the frames of CNF.generate(z, nframes) (src/flow.py:45-48)
 for a fresh batch of base walkers after the last iteration -- particles moving from the free-fermion base to the interacting state.
 `--frames_maps_out FILE.npz` writes the density maps (observables.DensityMaps) of the same walkers, one set per frame, binned on the
-device: without --frames_out no trajectory goes to the host.  The flags of the run's own maps (`--maps_out`) are declared here too."""
+device: without --frames_out no trajectory goes to the host.  The flags of the run's own maps (`--maps_out`) and of its one-body density
+matrix (`--obdm_out`, observables.OneBodyDensityMatrix) are declared here too."""
 import math
 
 import numpy as np
@@ -19,9 +20,24 @@ def add_arguments(parser):
     parser.add_argument("--maps_bins", type=int, default=128, help="cells per axis of the maps (at most 128)")
     parser.add_argument("--frames_maps_out", type=str, default=None,
                         help=".npz file for the density maps of every frame of the --frames_out trajectory's walkers (also without --frames_out)")
+    parser.add_argument("--obdm_out", type=str, default=None,
+                        help=".npz file for the one-body density matrix (natural occupations, n(k)) averaged over the run's iterations")
+    parser.add_argument("--obdm_shells", type=int, default=4, help="oscillator shells of the matrix's basis (1 .. 8)")
+    parser.add_argument("--obdm_sigma", type=float, default=1.0, help="width of the Gaussian the moved particle's position is drawn from")
+    parser.add_argument("--obdm_every", type=int, default=1, help="measure the matrix on every obdm_every-th iteration")
+    parser.add_argument("--obdm_stride", type=int, default=1, help="measure the matrix on every obdm_stride-th walker")
 
 
 def check_arguments(parser, args):
+    if args.obdm_out:
+        if getattr(args, "dim", 2) != 2:
+            parser.error("--obdm_out is measured in the two-dimensional oscillator basis: not with --dim 3")
+        if not 1 <= args.obdm_shells <= 8:
+            parser.error("--obdm_shells must be between 1 and 8")
+        if not (args.obdm_sigma > 0.0 and math.isfinite(args.obdm_sigma)):
+            parser.error("--obdm_sigma must be positive and finite")
+        if args.obdm_every < 1 or args.obdm_stride < 1:
+            parser.error("--obdm_every and --obdm_stride must be at least 1")
     if (args.frames_out or args.frames_maps_out) and args.nframes < 1:
         parser.error("--nframes must be at least 1")
     if (args.frames_out or args.frames_maps_out) and args.frames_batch < 1:
@@ -51,3 +67,19 @@ def write(args, frames, t_span, nup, ndown, dim):
         maps = DensityMaps(nup, ndown, extent=args.maps_extent, nbins=args.maps_bins, nframes=frames.shape[0], device=frames.device)
         maps.accumulate_frames(frames)
         maps.save_npz(args.frames_maps_out)
+
+
+def attach_obdm(args, model, nup, ndown, device):
+    """--obdm_out: the accumulator the sweeps of `model` feed (model.obdm)."""
+    if args.obdm_out:
+        from .observables import OneBodyDensityMatrix
+        model.obdm = OneBodyDensityMatrix(nup, ndown, nshells=args.obdm_shells, sigma=args.obdm_sigma, every=args.obdm_every,
+                                          stride=args.obdm_stride, device=device)
+
+
+def write_obdm(args, model, rank):
+    """After the last iteration: the sum over the ranks, then the file on rank 0."""
+    if args.obdm_out:
+        model.obdm.all_reduce_()
+        if rank == 0:
+            model.obdm.save_npz(args.obdm_out)

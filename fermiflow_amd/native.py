@@ -553,6 +553,34 @@ def beta_finish(buf, shift_dev, logits, beta, n_global):
     return est, gphi, mean_e, lpa
 
 
+# ---- one-body density matrix (include/fermiflow_obdm.h, csrc/ff_obdm.h) ---------------------------------
+def slater_sign(tab_up, tab_dn, nup, ndn, z, walker_state=None):
+    """ff_slater_sign: (B,) the sign of det Phi_up(z) det Phi_dn(z) under the walker's state, in {-1, 0, +1}; NaN for a walker with a
+    coordinate that is not finite."""
+    z = L.dev(z, name="z")
+    B = z.shape[0]
+    out = torch.empty(B, dtype=torch.float64, device=z.device)
+    L.check(L.lib().ff_slater_sign(L.stream(), B, nup, ndn, L.ptr(tab_up), L.ptr(tab_dn), L.ptr(_state(walker_state)), L.ptr(z), L.ptr(out)),
+            "ff_slater_sign")
+    return out
+
+
+def obdm_accumulate(nup, ndn, x, rprime, logp, sign, logp_moved, sign_moved, sigma, nshells, acc, workspace):
+    """ff_obdm_accumulate: one call = one block of the accumulator `acc` (int64 words, include/fermiflow_obdm.h); `workspace`: fp64
+    scratch of at least ff_obdm_workspace_bytes(B, nshells) bytes."""
+    x = L.dev(x, name="x")
+    B, n = x.shape[0], nup + ndn
+    t = [L.dev(v, name=k) for k, v in (("rprime", rprime), ("logp", logp), ("sign", sign), ("logp_moved", logp_moved), ("sign_moved", sign_moved))]
+    for v, shape, k in zip([x] + t, ((B, n, 2), (B, 2, 2), (B,), (B,), (B, n), (B, n)), ("x", "rprime", "logp", "sign", "logp_moved", "sign_moved")):
+        if tuple(v.shape) != shape:
+            raise ValueError(f"obdm_accumulate: {k} must be {shape}, got {tuple(v.shape)}")
+    need = L.lib().ff_obdm_workspace_bytes(B, int(nshells))
+    if need and workspace.numel() * 8 < need:
+        raise ValueError(f"obdm_accumulate: workspace of {workspace.numel() * 8} bytes, {need} needed")
+    L.check(L.lib().ff_obdm_accumulate(L.stream(), B, nup, ndn, L.ptr(x), *[L.ptr(v) for v in t], float(sigma), int(nshells),
+                                       L.ptr(L.dev(acc, torch.int64, "acc")), L.ptr(L.dev(workspace, name="workspace"))), "ff_obdm_accumulate")
+
+
 # ---- d = 3 (csrc/ff_ho3d.hip) ---------------------------------------------------------------------------
 def logprob3d(tab_up, tab_dn, nup, ndn, x, walker_state=None, derivs=False):
     x = L.dev(x, name="x")

@@ -19,6 +19,10 @@ Errors are block standard errors with one block per call (per rank and call afte
 
 DensityMaps (below) is the two-dimensional counterpart: the lab-frame density rho(x, y) of each species and the pair densities in the
 frame rotating with the reference particle, through ff_maps_accumulate (csrc/ff_maps.h, include/fermiflow_maps.h).
+
+OneBodyDensityMatrix (at the end) is the off-diagonal one: the one-body reduced density matrix in the oscillator basis from
+wave-function ratios with one particle moved -- natural occupations, n(k) -- through ff_slater_sign and ff_obdm_accumulate
+(csrc/ff_obdm.h, include/fermiflow_obdm.h).
 """
 import math
 
@@ -359,4 +363,248 @@ class DensityMaps:
                 out[("rho_" if name in PLANES[:2] else "g_") + name] = cnt.astype(np.float64) / (out["walkers"][:, None, None].astype(np.float64) * self.cell_area)
             out["counts_" + name] = cnt
             out["lost_" + name] = np.array([c["lost_" + name] for c in cs], dtype=np.int64)
+        np.savez(path, **out)
+
+
+# ---- one-body density matrix in the oscillator basis (include/fermiflow_obdm.h, csrc/ff_obdm.h) ----------------------------------
+OBDM_MAX_SHELLS = 8
+_OBDM_HEAD = 5                 # FF_OBDM_HEAD: calls, walkers, invalid[2], ticket
+OBDM_MAX_MOVED = 2 ** 22       # walkers of the moved batch of one measure()
+
+
+def ho2d_degrees(nshells):
+    """(nx, ny) of the first nshells (nshells + 1) / 2 orbitals in the HO2D list order."""
+    return [(nx, N - nx) for N in range(int(nshells)) for nx in range(N + 1)]
+
+
+def ho2d_basis(nshells, x, y):
+    """phi_k(x, y) = pi^-1/2 exp(-r^2 / 2) h_nx(x) h_ny(y) of the basis orbitals on the host: (nb, *shape) for broadcastable x, y."""
+    x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
+
+    def herm(t):
+        h = [np.ones_like(t), math.sqrt(2.0) * t]
+        for m in range(1, 7):
+            h.append(math.sqrt(2.0 / (m + 1)) * t * h[m] - math.sqrt(m / (m + 1.0)) * h[m - 1])
+        return h
+    hx, hy = herm(x), herm(y)
+    g = np.exp(-0.5 * (x * x + y * y)) / math.sqrt(math.pi)
+    return np.stack([g * hx[nx] * hy[ny] for nx, ny in ho2d_degrees(nshells)])
+
+
+class OneBodyDensityMatrix:
+    """The one-body reduced density matrix rho_1(r, r') of each spin species (d = 2) in the basis of the first
+    nb = nshells (nshells + 1) / 2 harmonic-oscillator orbitals, rho^s_ac = <phi_a| rho_1^s |phi_c>, accumulated on the device.  From it:
+    the natural occupation numbers (occupations()), the momentum distribution n(k) (momentum_distribution()) and the density
+    (density()).  tr rho^s -> N_s as the basis grows.
+
+        obdm = OneBodyDensityMatrix(nup, ndown, nshells=4)
+        model.obdm = obdm                    # GSVMC / BetaVMC: every `every`-th sweep measures, right after the local-energy pass
+        ...
+        occ, coeff = obdm.occupations()["up"]; n_k = obdm.momentum_distribution(kx, ky)["up"]
+
+    Estimator (include/fermiflow_obdm.h): for every walker x and species s ONE point r' is drawn from N(0, sigma^2 I); with x^(i) = x
+    with particle i of s moved to r' and q_i = psi(x^(i)) / psi(x), the walker adds (A C^T + C A^T) / 2, A_a = sum_i phi_a(x_i) q_i,
+    C_c = phi_c(r') / g(r').  The ratios need the flow integrated backwards for the n moved copies of every walker and the sign of the
+    Slater determinants (ff_slater_sign): measure() costs about n local backward flows per walker it takes, so `stride` thins the
+    walkers (0, stride, 2 stride, ...: a sorted walker_state stays sorted and keeps its proportions) and `every` the sweeps.
+
+    measure() and accumulate_raw() enqueue on torch's current stream and read nothing on the host; r' comes from a private
+    torch.Generator on the walkers' device, seeded with `seed` -- torch's CPU generator is never touched.  The host reads the buffer
+    only in counts() / matrix() / ... / state_dict() / all_reduce_() / save_npz().  Every call must bring the same number of walkers:
+    one call is one block of the block standard error (matrix_err(); NaN below two calls).  A result is bit-identical from run to run
+    on one device.  all_reduce_() adds the sums of the ranks as doubles, once, when the run is over: one block per rank and call,
+    and the sum is NOT bit-identical across rank counts (the counts are exact)."""
+
+    def __init__(self, nup, ndown, nshells=4, sigma=1.0, every=1, stride=1, seed=0, device=None):
+        nup, ndown, nshells, sigma, every, stride, seed = int(nup), int(ndown), int(nshells), float(sigma), int(every), int(stride), int(seed)
+        if nup < 0 or ndown < 0 or nup + ndown < 1:
+            raise ValueError("OneBodyDensityMatrix: nup, ndown >= 0 and at least one particle")
+        if not 1 <= nshells <= OBDM_MAX_SHELLS:
+            raise ValueError(f"OneBodyDensityMatrix: 1 <= nshells <= {OBDM_MAX_SHELLS}")
+        if not (sigma > 0.0 and math.isfinite(sigma)):
+            raise ValueError("OneBodyDensityMatrix: sigma must be positive and finite")
+        if every < 1 or stride < 1:
+            raise ValueError("OneBodyDensityMatrix: every and stride must be at least 1")
+        if nup + ndown > 24 or nup > 12 or ndown > 12:
+            raise NotImplementedError("OneBodyDensityMatrix: n <= 24 and at most 12 particles per species")
+        self.nup, self.ndown, self.nshells, self.sigma, self.every, self.stride, self.seed = nup, ndown, nshells, sigma, every, stride, seed
+        self.nb = nshells * (nshells + 1) // 2
+        self._E = 2 * self.nb * self.nb
+        self._words = _OBDM_HEAD + 2 * self._E      # include/fermiflow_obdm.h: [calls, walkers, invalid[2], ticket | sum | sumsq]
+        self._B = None
+        self._buf = None
+        self._ws = None
+        self._gen = None
+        self._cols = None
+        self._sweeps = 0
+        self._checked = False
+        self.last = None
+        if device is not None:
+            self._buf = torch.zeros(self._words, dtype=torch.int64, device=torch.device(device))
+
+    # ---- device side -------------------------------------------------------------------------------------------------------
+    def accumulate_raw(self, x, rprime, logp, sign, logp_moved, sign_moved):
+        """One ff_obdm_accumulate on the current stream: x (B, n, 2), rprime (B, 2, 2), logp (B), sign (B), logp_moved (B, n),
+        sign_moved (B, n), fp64 on the device.  One call is one block."""
+        from . import native
+        x = _lib.dev(x, name="x")
+        B = int(x.shape[0])
+        if self._B is not None and B != self._B:
+            raise ValueError(f"OneBodyDensityMatrix: {B} walkers, the earlier calls had {self._B} (the block errors need equal blocks)")
+        if self._buf is None or self._buf.device != x.device:
+            self._buf = torch.zeros(self._words, dtype=torch.int64, device=x.device) if self._buf is None else self._buf.to(x.device)
+        lib = _lib.lib()
+        if not self._checked:
+            if lib.ff_obdm_buffer_bytes(self.nshells) != 8 * self._words:
+                raise RuntimeError("OneBodyDensityMatrix: the library lays the accumulator out differently (include/fermiflow_obdm.h)")
+            self._checked = True
+        need = max(1, lib.ff_obdm_workspace_bytes(B, self.nshells) // 8)
+        if self._ws is None or self._ws.device != x.device or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.float64, device=x.device)
+        native.obdm_accumulate(self.nup, self.ndown, x, rprime, logp, sign, logp_moved, sign_moved, self.sigma, self.nshells, self._buf, self._ws)
+        if B > 0:
+            self._B = B
+
+    def measure(self, net, tab_up, tab_dn, x, z, logp, t_span, rtol, atol, walker_state=None):
+        """The whole pipeline for the walkers x (B, n, 2) of a sweep, z = z(t0) their base walkers and logp = log p(x): take every
+        `stride`-th walker, draw r', build the moved batch (B' n, n, 2), integrate it backwards (native.cnf_delta_logp), evaluate
+        log-density and sign of the moved and the unmoved base walkers, accumulate.  Nothing is read on the host.  `last` keeps
+        {rprime, logp_moved, sign_moved, sign, logp} of this call (the walkers it took) on the device."""
+        from . import native
+        n = self.nup + self.ndown
+        x = _lib.dev(x, name="x")
+        if x.dim() != 3 or x.shape[1] != n or x.shape[2] != 2:
+            raise ValueError(f"OneBodyDensityMatrix.measure: x must be (B, {n}, 2), got {tuple(x.shape)}")
+        s = self.stride
+        xs, zs, lps = x[::s].contiguous(), z[::s].contiguous(), logp[::s].contiguous()
+        ws = None if walker_state is None else walker_state[::s].contiguous()
+        B, dev = int(xs.shape[0]), x.device
+        if B * n > OBDM_MAX_MOVED:
+            raise ValueError(f"OneBodyDensityMatrix.measure: a moved batch of {B * n} walkers (more than 2^22): raise `stride` (now {s})")
+        if self._gen is None or self._gen.device != dev:
+            self._gen = torch.Generator(device=dev)
+            self._gen.manual_seed(self.seed)
+            ar = torch.arange(n, device=dev)
+            self._cols = (ar, (ar >= self.nup).to(torch.int64))          # particle -> its row, its species
+        rp = torch.randn(B, 2, 2, generator=self._gen, device=dev, dtype=torch.float64) * self.sigma
+        ar, species = self._cols
+        xm = xs[:, None].expand(B, n, n, 2).clone()                      # [walker, moved particle, row, coordinate]
+        xm[:, ar, ar] = rp[:, species]
+        xm = xm.view(B * n, n, 2)
+        wsm = None if ws is None else ws[:, None].expand(B, n).reshape(-1)      # walker-major: a sorted state list stays sorted
+        zm, dl = native.cnf_delta_logp(net, xm, float(t_span[0]), float(t_span[1]), rtol, atol)
+        lpm = (native.logprob(tab_up, tab_dn, self.nup, self.ndown, zm, wsm) - dl).view(B, n)
+        sgm = native.slater_sign(tab_up, tab_dn, self.nup, self.ndown, zm, wsm).view(B, n)
+        sg = native.slater_sign(tab_up, tab_dn, self.nup, self.ndown, zs, ws)
+        self.accumulate_raw(xs, rp, lps, sg, lpm, sgm)
+        self.last = {"rprime": rp, "logp_moved": lpm, "sign_moved": sgm, "sign": sg, "logp": lps}
+
+    def on_sweep(self, net, tab_up, tab_dn, x, z, logp, t_span, rtol, atol, walker_state=None):
+        """The sweeps' hook: measure() on every `every`-th call."""
+        k, self._sweeps = self._sweeps, self._sweeps + 1
+        if k % self.every == 0:
+            self.measure(net, tab_up, tab_dn, x, z, logp, t_span, rtol, atol, walker_state)
+
+    def reset(self):
+        if self._buf is not None:
+            self._buf.zero_()
+        self._B, self._sweeps = None, 0
+
+    def all_reduce_(self):
+        """Sum calls, walkers, invalid (exact below 2^53, it raises otherwise) and sum, sumsq (doubles) over the ranks of
+        torch.distributed through dist.all_reduce_sum_.  Call it once, when the run is over."""
+        if self._buf is None:
+            self._buf = torch.zeros(self._words, dtype=torch.int64)
+        t = torch.cat([self._buf[:4].to(torch.float64), self._buf[_OBDM_HEAD:].view(torch.float64)])
+        D.all_reduce_sum_(t)
+        if bool((t[:4] >= _EXACT).any()):
+            raise OverflowError("OneBodyDensityMatrix.all_reduce_: a count reached 2^53, the sum over ranks as doubles would not be exact")
+        self._buf[:4] = t[:4].to(torch.int64)
+        self._buf[_OBDM_HEAD:] = t[4:].view(torch.int64)
+        return self
+
+    # ---- host side ---------------------------------------------------------------------------------------------------------
+    def _host(self):
+        a = np.zeros(self._words, dtype=np.int64) if self._buf is None else self._buf.cpu().numpy().astype(np.int64)
+        f = a[_OBDM_HEAD:].view(np.float64)
+        nb, E = self.nb, self._E
+        return int(a[0]), int(a[1]), (int(a[2]), int(a[3])), f[:E].reshape(2, nb, nb).copy(), f[E:].reshape(2, nb, nb).copy()
+
+    def counts(self):
+        """{"calls", "walkers", "invalid_up", "invalid_down": samples (walker, particle) that were left out, "samples_up",
+        "samples_down": walkers x particles of the species}."""
+        calls, walkers, inv, _, _ = self._host()
+        return {"calls": calls, "walkers": walkers, "invalid_up": inv[0], "invalid_down": inv[1],
+                "samples_up": walkers * self.nup, "samples_down": walkers * self.ndown}
+
+    def matrix(self):
+        """{"up", "down"}: rho^s (nb, nb), symmetric."""
+        _, walkers, _, s, _ = self._host()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return {"up": s[0] / float(walkers), "down": s[1] / float(walkers)}
+
+    def matrix_err(self):
+        """{"up", "down"}: the block standard error of every entry, one block per call (NaN below two calls)."""
+        calls, walkers, _, s, q = self._host()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if calls >= 2:
+                m = float(calls)
+                var = np.maximum(q / m - (s / m) ** 2, 0.0) * (m / (m - 1.0))
+                err = np.sqrt(var / m) / (float(walkers) / m)
+            else:
+                err = np.full_like(s, np.nan)
+        return {"up": err[0], "down": err[1]}
+
+    def occupations(self):
+        """{"up", "down"}: (occ (nb,) the natural occupation numbers in descending order, coeff (nb, nb): column k holds the
+        coefficients of natural orbital k in the basis) -- numpy.linalg.eigh of rho^s."""
+        out = {}
+        for name, rho in self.matrix().items():
+            w, v = np.linalg.eigh(rho)
+            out[name] = (w[::-1].copy(), v[:, ::-1].copy())
+        return out
+
+    def degrees(self):
+        return ho2d_degrees(self.nshells)
+
+    def momentum_distribution(self, kx, ky):
+        """{"up", "down"}: n_s(k) = sum_ac rho_ac cos(pi (N_c - N_a) / 2) phi_a(k) phi_c(k), N = nx + ny (an oscillator
+        eigenfunction is its own Fourier transform up to (-i)^N); its integral over the plane is tr rho^s."""
+        phi = ho2d_basis(self.nshells, kx, ky)
+        N = np.array([nx + ny for nx, ny in self.degrees()])
+        ph = np.cos(0.5 * math.pi * (N[None, :] - N[:, None]))
+        return {name: np.einsum("ac,a...,c...->...", rho * ph, phi, phi) for name, rho in self.matrix().items()}
+
+    def density(self, x, y):
+        """{"up", "down"}: rho_s(r) = sum_ac rho_ac phi_a(r) phi_c(r), the density as the basis resolves it."""
+        phi = ho2d_basis(self.nshells, x, y)
+        return {name: np.einsum("ac,a...,c...->...", rho, phi, phi) for name, rho in self.matrix().items()}
+
+    def state_dict(self):
+        acc = torch.zeros(self._words, dtype=torch.int64) if self._buf is None else self._buf.cpu().clone()
+        return {"nup": self.nup, "ndown": self.ndown, "nshells": self.nshells, "sigma": self.sigma, "acc": acc}
+
+    def load_state_dict(self, st):
+        for k in ("nup", "ndown", "nshells", "sigma"):
+            if st[k] != getattr(self, k):
+                raise ValueError(f"OneBodyDensityMatrix.load_state_dict: {k} = {st[k]!r}, this object has {getattr(self, k)!r}")
+        acc = torch.as_tensor(st["acc"]).to(torch.int64).reshape(-1)
+        if acc.numel() != self._words:
+            raise ValueError(f"OneBodyDensityMatrix.load_state_dict: {acc.numel()} words, expected {self._words}")
+        if self._buf is None:
+            self._buf = torch.zeros(self._words, dtype=torch.int64)
+        self._buf.copy_(acc.to(self._buf.device))
+        calls, walkers = int(acc[0]), int(acc[1])
+        self._B = walkers // calls if calls > 0 else None
+
+    def save_npz(self, path):
+        """One .npz (what the drivers' --obdm_out writes): rho_<s>, err_<s>, occ_<s>, natorb_<s>, the raw sums, the counts, the
+        degrees (nx, ny) of the basis and the settings."""
+        calls, walkers, inv, s, q = self._host()
+        rho, err, occ = self.matrix(), self.matrix_err(), self.occupations()
+        out = dict(calls=calls, walkers=walkers, invalid=np.array(inv, dtype=np.int64), sum=s, sumsq=q, degrees=np.array(self.degrees(), dtype=np.int64),
+                   nup=self.nup, ndown=self.ndown, nshells=self.nshells, sigma=self.sigma, every=self.every, stride=self.stride, seed=self.seed)
+        for name in ("up", "down"):
+            out["rho_" + name], out["err_" + name] = rho[name], err[name]
+            out["occ_" + name], out["natorb_" + name] = occ[name]
         np.savez(path, **out)
