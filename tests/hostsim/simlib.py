@@ -244,16 +244,26 @@ def eloc(x, nup, ndn, net, Z, use_ho=True, t0=0.0, t1=1.0, rtol=1e-6, atol=1e-8,
     return o
 
 
-def eloc_nd(x, nup, ndn, net, Z, use_ho=True, t0=0.0, t1=1.0, rtol=1e-6, atol=1e-8, tab_up=None, tab_dn=None, wstate=None, compact=True):
-    """ff_eloc_nd (d from x) with ff_ode.compact_finish; z / dlogp are read from the head of the workspace."""
+def eloc_nd(x, nup, ndn, net, Z, use_ho=True, t0=0.0, t1=1.0, rtol=1e-6, atol=1e-8, tab_up=None, tab_dn=None, wstate=None, compact=True,
+            order=None, two_pass=False):
+    """ff_eloc_nd (d from x) with ff_ode.compact_finish; z / dlogp are read from the head of the workspace.
+    two_pass: ff_eloc_sensitivities + ff_eloc_finish / ff_eloc_finish3d instead (the unfused route; not with compact)."""
     x = _d(x); B, n, d = x.shape
     tu, td = _tabs(nup, ndn, tab_up, tab_dn); ws = _i(wstate) if wstate is not None else None
     o = dict(logp=np.empty(B), grad=np.empty_like(x), lap=np.empty(B), V=np.empty(B), eloc=np.empty(B), glogp0=np.empty_like(x))
-    stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol, compact=compact)
-    nb = lib().ff_eloc_nd_workspace_bytes(B, n, d, int(bool(compact)))
+    od = _i(order) if order is not None else None      # (kept alive: the ff_ode holds its address)
+    stats = np.zeros(4, dtype=np.int32); ode = _ode(t0, t1, rtol, atol, order=od, compact=compact)
+    assert not (two_pass and compact)
+    nb = lib().ff_eloc_workspace_bytes(B, n, d) if two_pass else lib().ff_eloc_nd_workspace_bytes(B, n, d, int(bool(compact)))
     wk = np.zeros(nb // 8)
-    _ck(lib().ff_eloc_nd(None, B, nup, ndn, d, _p(tu), _p(td), _p(ws), C.byref(net.c), C.byref(ode), Z, int(use_ho), _p(x), _p(o["logp"]), _p(o["grad"]),
-                         _p(o["lap"]), _p(o["V"]), _p(o["eloc"]), None, None, _p(o["glogp0"]), _p(wk), _p(stats)))
+    if two_pass:
+        _ck(lib().ff_eloc_sensitivities(None, B, n, d, C.byref(net.c), C.byref(ode), _p(x), _p(wk), _p(stats)))
+        _ck((lib().ff_eloc_finish3d if d == 3 else lib().ff_eloc_finish)(
+            None, B, nup, ndn, _p(tu), _p(td), _p(ws), Z, int(use_ho), _p(x), _p(wk), _p(o["logp"]), _p(o["grad"]), _p(o["lap"]), _p(o["V"]),
+            _p(o["eloc"]), None, None, _p(o["glogp0"])))
+    else:
+        _ck(lib().ff_eloc_nd(None, B, nup, ndn, d, _p(tu), _p(td), _p(ws), C.byref(net.c), C.byref(ode), Z, int(use_ho), _p(x), _p(o["logp"]),
+                             _p(o["grad"]), _p(o["lap"]), _p(o["V"]), _p(o["eloc"]), None, None, _p(o["glogp0"]), _p(wk), _p(stats)))
     M = n * d
     o["z"] = wk[:B * M].reshape(B, n, d).copy()
     dl0 = B * M if (compact and M > 24) else B * (M * M + 4 * M)
