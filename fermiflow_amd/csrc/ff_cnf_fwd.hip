@@ -53,12 +53,17 @@
 #ifndef FF_FWD_WAVES_PER_SIMD
 #define FF_FWD_WAVES_PER_SIMD 1
 #endif
-// The tabulated flow kernel (MODE 0) carries one double per lane and hides its table fetches behind other waves: up to 6 particles it
-// is compiled for three waves per SIMD (<= 168 registers, no scratch; left alone hipcc drifted from 159 to 169 registers
-// with an unrelated change and the flow pass went from 112 to 143 us).  Larger walkers and delta_logp (MODE 1) would spill
-// under that bound; the local-energy kernel (MODE 2) needs the whole register file.
+// The tabulated flow kernel (MODE 0, and its frames twin) carries one double per lane and hides its table fetches behind other waves:
+// up to 12 coordinates it is compiled for four waves per SIMD (<= 128 registers).  A bound alone does not give that -- the allocator
+// meets it by spilling -- so what the head and the tail of a walker group need is kept out of the step loop's registers (LEAN,
+// DESIGN.md 3ad): 95-116 registers for generate (6 x 2: 116), 101-127 for the frames twin (6 x 2: 127), no scratch;
+// tests/test_flow_waves_occupancy.py holds the built library to it.  Measured at 6 x 2, 65 536 walkers: three waves (142 registers)
+// 108.6 us, four 98.2 us; before the diet four waves meant 128 registers + 44 B of scratch, and left alone hipcc once drifted from
+// 159 to 169 registers (two waves) with an unrelated change: 112 -> 143 us.  Larger walkers keep the one-wave bound (their registers
+// give them two or three waves: 7 x 2 114, 12 x 2 147); delta_logp (MODE 1) would spill under a bound of three; the local-energy
+// kernel (MODE 2) needs the whole register file.
 #ifndef FF_FLOW_WAVES
-#define FF_FLOW_WAVES 3      // waves per SIMD the tabulated flow kernel is compiled for (165 registers; 4: 128 + 140 B of scratch, 5: 95 + 280 B)
+#define FF_FLOW_WAVES 4      // waves per SIMD the tabulated flow kernel is compiled for (3: 142 registers at 6 x 2 before the diet)
 #endif
 // instantiations whose step is laid out stage by stage (compile-time stages: DESIGN.md 3s)
 #ifndef FF_FWD_STATIC
@@ -115,6 +120,7 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
   static_assert(MODE != 2 || M <= 12, "the column-sweep local-energy kernel serves at most 12 coordinates");
   constexpr bool LDS_STATE = (MODE == 2);
   __shared__ double s_yv[LDS_STATE ? NV : 1][FF_WAVE], s_cv[LDS_STATE ? NV : 1][FF_WAVE];
+  __shared__ double s_open[LEAN ? 3 : 1][LEAN ? FF_WAVE : 1];      // (LEAN: the opening scalars of a lane's integration, below)
 
   const int lane = threadIdx.x;
   const int g = lane / M, i = lane % M;
@@ -187,9 +193,18 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
       if (lane == 0) s_next = (long long)atomicAdd(A.queue + (TAB ? 0 : 1), 1ULL);
       FF_WG1_SYNC();
       grp = s_next;
+      if constexpr (LEAN) {      // uniform: kept in scalar registers across the step loop, not in a vector pair
+        grp = (int64_t)(((uint64_t)(uint32_t)FF_UNIFORM((int)((uint64_t)grp >> 32)) << 32) | (uint32_t)FF_UNIFORM((int)grp));
+      }
     }
     if (grp >= ngroups) break;
-    const int64_t bq = grp * G + g;
+    // LEAN: what only the head and the tail of a walker group use -- the walker's index, the addresses and the idle
+    // rows' stand-in value of its lanes -- is derived from a lane id laundered at the spot, so none of it is hoisted in front of the
+    // persistent loop and carried (in registers, or spilled) across the step loop.  The same values by the same operations.
+    // (Everything of it sits behind LEAN: the other instantiations read the text they always did.)
+    int lh = 0;
+    if constexpr (LEAN) { lh = lane; FF_OPAQUE(lh); }
+    const int64_t bq = grp * G + (LEAN ? lh / M : g);
     const bool inb = ingrp && bq < A.B;
     const int64_t b = ff_opt_load(A.order, inb, bq, A.y_in, (int32_t)bq);   // the walker this lane group integrates
     // (routing by cost class, launch_routed below: with heavy_mode = 2 the walkers of class >= heavy_class belong to another launch)
@@ -207,6 +222,10 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
     double c0[NV], c1[NV], c2[NV];
 #pragma unroll
     for (int v = 0; v < NV; v++) { y[v] = 0.0; c0[v] = 0.0; c1[v] = 0.0; c2[v] = 0.0; c3[v] = 0.0; }
+    if constexpr (LEAN) {
+      const int ih = lh % M;
+      y[0] = ff_opt_load(A.y_in, valid, b * M + ih, A.y_in, 0.25 * (ih + 1) + 0.125 * ((ih * 7) % 5));
+    } else
     y[0] = ff_opt_load(A.y_in, valid, b * M + i, A.y_in, 0.25 * (i + 1) + 0.125 * ((i * 7) % 5));  // idle rows: finite, distinct
     if constexpr (MODE == 2) {
 #pragma unroll
@@ -215,19 +234,30 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
     std::conditional_t<FRAMES, ff_frame_stepper, ff_stepper> S;
     if constexpr (FRAMES) {
       S.begin(A.ta, A.tb, valid, A.nframes);
-      if (valid) A.y_out[b * M + i] = y[0];   // frame 0
+      if (valid) A.y_out[b * M + (LEAN ? lh % M : i)] = y[0];   // frame 0
     } else {
       S.begin(A.ta, A.tb, valid);
     }
+    // (LEAN: tb - ta is uniform but lives in a vector register; formed here per group, from a laundered ta, it is the stepper's
+    // interval and nothing else -- the copy hoisted in front of the persistent loop had to be carried across the step loop beside it)
+    double tah = 0.0;
+    if constexpr (LEAN) { tah = A.ta; FF_OPAQUE(tah); S.interval = fabs(A.tb - tah); }
     // warm start (ff_ode.walker_h_init): the step size to try first, instead of the probe evaluation of the Hairer start
     // (local-energy pass) walkers of a low cost class: looser tolerance for the sensitivity components, larger first step
     const bool loose = MODE == 2 && ff_opt_load(A.wclass, valid, b, A.y_in, (int32_t)0x7fffffff) <= A.sens_class;
     const double hwarm = ff_open_step(ff_opt_load(A.h_init, valid, A.h_scale < 0.0 ? 0 : b, A.y_in, 0.0) * (loose ? A.h_scale_loose : fabs(A.h_scale)),
-                                      A.ta, A.tb, MODE == 2 ? 0 : A.h_equal);
+                                      LEAN ? tah : A.ta, A.tb, MODE == 2 ? 0 : A.h_equal);
     const bool warm = hwarm > 0.0;
     double hmax_acc = 0.0;
     int s = -2, nev = 0;
     double h0v = 0.0, d1v = 0.0;
+    // LEAN: the scalars of the opening of an integration -- the warm-start step, and h0 and d1 between the two probe evaluations -- sit
+    // in a lane-private LDS column (FF_OPEN_*: slot, or the register of the other instantiations): the evaluations in front of a step
+    // and the tail read them, the six stages of a step do not
+    if constexpr (LEAN) s_open[0][threadIdx.x] = hwarm;
+#define FF_OPEN_HWARM (LEAN ? s_open[0][threadIdx.x] : hwarm)
+#define FF_OPEN_H0V (LEAN ? s_open[1][threadIdx.x] : h0v)
+#define FF_OPEN_D1V (LEAN ? s_open[2][threadIdx.x] : d1v)
     double rmin_q[NQ];   // this lane's radii keep their slots from evaluation to evaluation
 #pragma unroll
     for (int k = 0; k < NQ; k++) rmin_q[k] = 1e300;
@@ -266,7 +296,7 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
       // (c1..c3 are zero-initialised, so unused terms are exact zeros)
       double gy = 1.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
       switch (sv) {
-        case -1: g0 = h0v * S.dir; break;
+        case -1: g0 = FF_OPEN_H0V * S.dir; break;
         case 1: g0 = h * FF_A10; break;
         case 2: g0 = h * FF_A20; g1 = h * FF_A21; break;
         case 3: g0 = h * FF_A30; g1 = h * FF_A31; g2 = h * FF_A32; break;
@@ -529,12 +559,12 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
           p1 = fma(c0[v] * isc, c0[v] * isc, p1);
         }
         const double d0 = sqrt(group_sum(p0) * (1.0 / NT));
-        d1v = sqrt(group_sum(p1) * (1.0 / NT));
-        h0v = S.h0(d0, d1v);
+        FF_OPEN_D1V = sqrt(group_sum(p1) * (1.0 / NT));
+        FF_OPEN_H0V = S.h0(d0, FF_OPEN_D1V);
         s = -1;
         // every walker of the wave brings its own first step: no probe evaluation
         if (!ff_wave_or(&s_any, lane, (!S.done && !warm) ? 1 : 0)) {
-          S.habs = fmin(hwarm, S.interval);
+          S.habs = fmin(FF_OPEN_HWARM, S.interval);
           S.plan();
           s = 1;
         }
@@ -545,9 +575,9 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
           const double t = (out[v] - c0[v]) * wgt(v) * ff_rcp(fma(fabs(y[v]), rtol, atol));
           p2 = fma(t, t, p2);
         }
-        const double d2 = sqrt(group_sum(p2) * (1.0 / NT)) / h0v;
-        S.init_habs(h0v, d1v, d2);
-        if (warm) S.habs = fmin(hwarm, S.interval);
+        const double d2 = sqrt(group_sum(p2) * (1.0 / NT)) / FF_OPEN_H0V;
+        S.init_habs(FF_OPEN_H0V, FF_OPEN_D1V, d2);
+        if (warm) S.habs = fmin(FF_OPEN_HWARM, S.interval);
         S.plan();
         s = 1;
       } else if (sv == 0) {
@@ -643,10 +673,24 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
     if (A.wcost) {   // wave-uniform
 #pragma unroll
       for (int qk = 0; qk < NQ; qk++) {
+        if constexpr (LEAN) {      // (the slot of radius q = lane + 64 qk again as rq_id had it -- walker q / nrad, radius q mod nrad -- from
+          int q = lane;            //  a laundered lane: neither the packed id nor an address per slot is carried across the step loop)
+          FF_OPAQUE(q);
+          q += qk * FF_WAVE;
+          const int qg = has_mu ? q / (P + N) : q / (P > 0 ? P : 1);
+          if (q < G * nrad) s_rmin[qg][q - qg * nrad] = rmin_q[qk];
+        } else
         if (rq_id[qk] >= 0) s_rmin[rq_id[qk] & 15][rq_id[qk] >> 12] = rmin_q[qk];
       }
       FF_WG1_SYNC();
     }
+    // (LEAN: the tail's lane indices and walker offset likewise, from values laundered behind the step loop)
+    int lt = 0;
+    int64_t bt = 0;
+    if constexpr (LEAN) { lt = lane; bt = b; FF_OPAQUE(lt); FF_OPAQUE(bt); }
+#define FF_TAIL_G (LEAN ? lt / M : g)
+#define FF_TAIL_I (LEAN ? lt % M : i)
+#define FF_TAIL_B (LEAN ? bt : b)
     if (valid) {
       // a walker whose integration failed (NaN error norm, max_steps) must not pass for a result: its outputs are NaN,
       // which every consumer (finish kernel, estimator, parameter gradient) propagates -- the stats word is only a diagnostic
@@ -657,9 +701,9 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
       const double bad = failed ? __builtin_nan("") : 0.0;
 #endif
       if constexpr (FRAMES) {   // the frames the walker did not reach: NaN after a failure (an empty interval: the state itself)
-        for (int k = S.kf; k < A.nframes; k++) A.y_out[((int64_t)k * A.B + b) * M + i] = y[0] + bad;
+        for (int k = S.kf; k < A.nframes; k++) A.y_out[((int64_t)k * A.B + FF_TAIL_B) * M + FF_TAIL_I] = y[0] + bad;
       } else {
-        A.y_out[b * M + i] = y[0] + bad;
+        A.y_out[FF_TAIL_B * M + FF_TAIL_I] = y[0] + bad;
       }
       if constexpr (MODE >= 1) { if (i == 0) A.dl_out[b] = y[IDL] + bad; }
       if constexpr (MODE == 2) {
@@ -669,17 +713,23 @@ ff_ode_fwd_kernel(ff_fwd_args A) {
         A.dD[b * M + i] = y[M + 2];
         A.Lpart[b * M + i] = y[M + 4];
       }
-      if (i == 0) {
-        if (A.h_out) A.h_out[b] = hmax_acc > 0.0 ? hmax_acc : hwarm;
+      if (FF_TAIL_I == 0) {
+        if (A.h_out) A.h_out[FF_TAIL_B] = hmax_acc > 0.0 ? hmax_acc : FF_OPEN_HWARM;
         if (A.wcost) {
           double rm = 1e300;
-          for (int p = 0; p < nrad; p++) rm = fmin(rm, s_rmin[g][p]);
-          A.wcost[b] = ff_cost_class(S.nacc + S.nrej, rm);
+          for (int p = 0; p < nrad; p++) rm = fmin(rm, s_rmin[FF_TAIL_G][p]);
+          A.wcost[FF_TAIL_B] = ff_cost_class(S.nacc + S.nrej, rm);
         }
         if (A.stats) { atomicAdd(&s_st[0], nev); atomicMax(&s_st[1], S.nacc); atomicAdd(&s_st[2], S.nrej); if (failed) atomicMax(&s_st[3], 1); }
       }
     }
     FF_WG1_SYNC();
+#undef FF_OPEN_HWARM
+#undef FF_OPEN_H0V
+#undef FF_OPEN_D1V
+#undef FF_TAIL_G
+#undef FF_TAIL_I
+#undef FF_TAIL_B
   }
 #ifdef FF_STAMPS
   if (A.stats && lane == 0)
