@@ -86,6 +86,7 @@ def main(argv=None):
     if args.maps_out:
         model.density_maps = DensityMaps(args.nup, args.ndown, extent=args.maps_extent, nbins=args.maps_bins, device=device)
     frames.attach_obdm(args, model, args.nup, args.ndown, device)
+    frames.attach_energy(args, model, args.nup, args.ndown, device)
     start_iter = 1
     if args.resume:
         start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None,
@@ -119,6 +120,7 @@ def main(argv=None):
         if rank == 0:
             model.density_maps.save_npz(args.maps_out)
     frames.write_obdm(args, model, rank)
+    frames.write_energy(args, model, rank)
     if args.frames_out or args.frames_maps_out:
         zx = model._sample_on_root((args.frames_batch,), nframes=args.nframes)      # (every rank: the state list is broadcast)
         if rank == 0:

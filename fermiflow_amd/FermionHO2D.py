@@ -99,6 +99,7 @@ def main(argv=None):
     if args.maps_out:
         model.density_maps = DensityMaps(args.nup, args.ndown, extent=args.maps_extent, nbins=args.maps_bins, device=device)
     frames.attach_obdm(args, model, args.nup, args.ndown, device)
+    frames.attach_energy(args, model, args.nup, args.ndown, device)
     start_iter = 1
     if args.resume:
         start_iter = checkpoint.load(args.resume, model, optimizer, device, observables=model.observables if rank == 0 else None,
@@ -129,6 +130,7 @@ def main(argv=None):
         if rank == 0:
             model.density_maps.save_npz(args.maps_out)
     frames.write_obdm(args, model, rank)
+    frames.write_energy(args, model, rank)
     if (args.frames_out or args.frames_maps_out) and rank == 0:
         z = basedist.sample(model.orbitals_up, model.orbitals_down, (args.frames_batch,))
         frames.write(args, cnf.generate(z, nframes=args.nframes), cnf.t_span, args.nup, args.ndown, args.dim)

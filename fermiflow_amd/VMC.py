@@ -158,6 +158,10 @@ class _Sweep:
         # not sweep state; None: not a launch changes
         self._sweep_dim = dim
         self.obdm = None
+        # None, or an observables.EnergyParts: every sweep then adds the energy components of its walkers (kinetic by two estimators, trap,
+        # interaction by spin pair) to it, one launch right after the local-energy pass (two with per-state sums).  A setting, not sweep
+        # state; None: not a launch changes.  The raw energies with invalid walkers dropped, whatever clip_eloc is.
+        self.energy_parts = None
         # None, or an sr.SR (GSVMC only): every sweep then also leaves the Fisher matrix of the walkers' log-derivatives on it (_sweep)
         self.sr = None
         # None, or a finite k > 0 (GSVMC only): the robust estimator -- failed walkers (a non-finite E_loc or logp) are dropped and the local
@@ -249,6 +253,8 @@ class _Sweep:
         prof = self.profile
         nloc = z.shape[0]
         t0, t1 = self.cnf.t_span
+        if self.energy_parts is not None:      # (checked when it was set, and again here: the potentials are attributes too)
+            self._check_energy_parts(self.energy_parts)
         cost = torch.empty(nloc, dtype=torch.int32, device=z.device)
         warm = self.warm_start
         hg = torch.empty(nloc, dtype=torch.float64, device=z.device) if warm else None
@@ -305,6 +311,8 @@ class _Sweep:
                         sens_tol_class=self.sens_tol_class, walker_h_scale_loose=1.0 if hs is not None else self._h_scale_loose,
                         heavy_class=self.heavy_class, heavy_tol=self.heavy_tol, sum_weight=self.sum_weight,
                         compact=self.compact_finish)
+        if self.energy_parts is not None:
+            self.energy_parts.accumulate_raw(x, r["grad"], r["lap"], walker_state if self.energy_parts.nstates > 0 else None)
         self._h_counts_local = None
         if hs is not None:
             if D._active():
@@ -365,6 +373,23 @@ class _Sweep:
         if obj is not None and self.__dict__.get("_sweep_dim", 2) != 2:
             raise NotImplementedError("obdm: the one-body density matrix is measured in the two-dimensional oscillator basis, this model has dim = 3")
         self.__dict__["_obdm"] = obj
+
+    @property
+    def energy_parts(self):
+        return self.__dict__.get("_energy_parts")
+
+    @energy_parts.setter
+    def energy_parts(self, obj):
+        if obj is not None:
+            self._check_energy_parts(obj)
+        self.__dict__["_energy_parts"] = obj
+
+    def _check_energy_parts(self, obj):
+        """ValueError unless the model's Hamiltonian is the one `obj` decomposes: HO() and CoulombPairPotential(obj.Z), its particle numbers
+        and dimension, and -- for an object with per-state sums -- this model's number of many-body states.  No launch."""
+        es = getattr(self, "Es_original", None)
+        obj.check_hamiltonian(*potential_plan(self.pair_potential, self.sp_potential), self.nup, self.ndown, self.__dict__.get("_sweep_dim", 2),
+                              nstates=None if es is None else len(es))
 
     def _scalar(self, key):
         return self._dev[key].item()

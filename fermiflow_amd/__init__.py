@@ -18,6 +18,6 @@ from .potentials import HO, CoulombPairPotential        # noqa: E402,F401
 from .VMC import GSVMC, BetaVMC                         # noqa: E402,F401
 from .utils import y_grad_laplacian                     # noqa: E402,F401
 from .NeuralODE.nnModule import solve_ivp_nnmodule      # noqa: E402,F401
-from .observables import DensityMaps, Observables, OneBodyDensityMatrix                    # noqa: E402,F401
+from .observables import DensityMaps, EnergyParts, Observables, OneBodyDensityMatrix                    # noqa: E402,F401
 from .sr import SR, BetaSR                              # noqa: E402,F401
 from . import checkpoint                                # noqa: E402,F401

@@ -1,5 +1,5 @@
 """The C ABI of include/fermiflow.h (and of include/fermiflow_robust.h: ROBUST_SIGNATURES; include/fermiflow_maps.h: MAPS_SIGNATURES;
-include/fermiflow_obdm.h: OBDM_SIGNATURES) as ctypes sees it: its three structs and the
+include/fermiflow_obdm.h: OBDM_SIGNATURES; include/fermiflow_energy.h: ENERGY_SIGNATURES) as ctypes sees it: its three structs and the
 signature of every function, declared once.
 fermiflow_amd._lib binds libfermiflow_hip.so to this table and tests/hostsim/simlib.py the host simulator's build of the same sources;
 tests/test_host_logic.py holds the table to the header, prototype by prototype.  Imports nothing but ctypes."""
@@ -104,12 +104,20 @@ OBDM_SIGNATURES = {
 }
 OBDM_MAX_SHELLS, OBDM_CHUNK, OBDM_HEAD = 8, 256, 5      # FF_OBDM_MAX_SHELLS, FF_OBDM_CHUNK, FF_OBDM_HEAD
 
+# include/fermiflow_energy.h, the fifth public header (energy components), in its order
+ENERGY_SIGNATURES = {
+    "ff_energy_parts_buffer_bytes": (_Z, (_I,)), "ff_energy_parts_workspace_bytes": (_Z, (_Q, _I)),
+    "ff_energy_parts_accumulate": (_I, (_P, _Q, _I, _I, _I, _D, _P, _P, _P, _P, _I, _P, _P, _P, _P)),
+}
+# FF_ENERGY_PARTS, FF_ENERGY_CHUNK, FF_ENERGY_PARTIAL, FF_ENERGY_HEAD, FF_ENERGY_FIXED, FF_ENERGY_MAX_STATES
+ENERGY_PARTS, ENERGY_CHUNK, ENERGY_PARTIAL, ENERGY_HEAD, ENERGY_FIXED, ENERGY_MAX_STATES = 6, 256, 28, 4, 52, 65536
+
 
 def bind(cdll):
-    """Set restype and argtypes of every function of SIGNATURES, ROBUST_SIGNATURES, MAPS_SIGNATURES and OBDM_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
+    """Set restype and argtypes of every function of SIGNATURES, ROBUST_SIGNATURES, MAPS_SIGNATURES, OBDM_SIGNATURES and ENERGY_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
     host simulator has no ff_comm_*; an A/B build of an earlier commit may lack the newest) is skipped and fails where it is called, as
     any missing symbol."""
-    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES, **MAPS_SIGNATURES, **OBDM_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES, **MAPS_SIGNATURES, **OBDM_SIGNATURES, **ENERGY_SIGNATURES}.items():
         fn = getattr(cdll, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

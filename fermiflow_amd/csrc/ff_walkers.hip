@@ -682,6 +682,8 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
 #include "ff_maps.h"
 // one-body density matrix in the oscillator basis and the sign of the Slater determinants (include/fermiflow_obdm.h)
 #include "ff_obdm.h"
+// energy components of the physical walkers: kinetic by two estimators, trap, Coulomb repulsion by spin pair (include/fermiflow_energy.h)
+#include "ff_energy_parts.h"
 // the opt-in robust estimator: median by radix select, clipped local energies, gradient weights (ff_energy_robust, include/fermiflow_robust.h)
 #include "ff_robust.h"
 
@@ -1378,6 +1380,51 @@ int ff_obdm_accumulate(void* stream, int64_t B, int nup, int ndn, const double* 
                 nup + ndn, x, rprime, logp, sign, logp_moved, sign_moved, 2.0 * sigma * sigma, 6.283185307179586 * sigma * sigma, nshells,
                 lgslab, (unsigned long long*)acc, (double*)workspace);
   FF_LAUNCH_CHECK();
+  return FF_OK;
+}
+
+size_t ff_energy_parts_buffer_bytes(int nstates) {
+  if (nstates < 0 || nstates > FF_ENERGY_MAX_STATES) return 0;
+  return sizeof(double) * (FF_ENERGY_FIXED + 8 * (size_t)nstates);
+}
+
+size_t ff_energy_parts_workspace_bytes(int64_t B, int nstates) {
+  if (nstates < 0 || nstates > FF_ENERGY_MAX_STATES || B < 0 || B >= ((int64_t)1 << 31)) return 0;
+  const size_t nchunks = B > 0 ? (size_t)((B + FF_ENERGY_CHUNK - 1) / FF_ENERGY_CHUNK) : 1;
+  return sizeof(double) * (nchunks * FF_ENERGY_PARTIAL + (nstates > 0 ? (size_t)B * FF_ENERGY_PARTS : 0));
+}
+
+int ff_energy_parts_accumulate(void* stream, int64_t B, int nup, int ndn, int d, double Z, const double* x, const double* grad,
+                               const double* lap, const int32_t* walker_state, int nstates, const double* centre, double* parts_out,
+                               void* acc, void* workspace) {
+  FF_CHECK(B >= 0 && nup >= 0 && ndn >= 0 && (int64_t)nup + ndn >= 1 && d >= 1 && nstates >= 0 && acc &&
+           (B == 0 || (x && grad && lap && workspace && (nstates == 0 || walker_state))), FF_EINVAL, "ff_energy_parts: bad argument");
+  FF_CHECK(fabs(Z) <= 1.7976931348623157e308, FF_EINVAL, "ff_energy_parts: Z must be finite");
+  FF_CHECK(d == 2 || d == 3, FF_EUNSUPPORTED, "ff_energy_parts: d must be 2 or 3");
+  FF_CHECK((int64_t)nup + ndn <= FF_MAX_N && ((int64_t)nup + ndn) * d <= FF_EP_MAX_COORD, FF_EUNSUPPORTED, "ff_energy_parts: n > 24 or n d > 60");
+  FF_CHECK(B < ((int64_t)1 << 31), FF_EUNSUPPORTED, "ff_energy_parts: B >= 2^31");
+  FF_CHECK(nstates <= FF_ENERGY_MAX_STATES, FF_EUNSUPPORTED, "ff_energy_parts: nstates > 65536");
+  if (B == 0) return FF_OK;
+  const int n = nup + ndn, M = n * d;
+  const int64_t nchunks = (B + FF_ENERGY_CHUNK - 1) / FF_ENERGY_CHUNK;
+  // a wave's region holds its tile's staged rows, then its 64 rows of centred components
+  const int rows = FF_WAVE * (M | 1), region = rows > FF_WAVE * FF_EP_ROW ? rows : FF_WAVE * FF_EP_ROW;
+  const size_t seg_bytes = sizeof(double) * FF_EP_NSEG * FF_ENERGY_PARTIAL;
+  int nwave = 4;
+  while (nwave > 1 && seg_bytes + sizeof(double) * (size_t)nwave * region > FF_EP_LDS_BYTES) nwave >>= 1;
+  const unsigned magic = (unsigned)((((uint64_t)1 << 32) + (uint64_t)M - 1) / (uint64_t)M);
+  double* const ws = (double*)workspace;
+  double* const parts_ws = nstates > 0 ? ws + nchunks * FF_ENERGY_PARTIAL : nullptr;
+  const unsigned grid = ff_grid(nchunks, 1, ff_device_cus() * FF_EP_GRID_PER_CU);
+  FF_LAUNCH_LDS(ff_energy_parts_kernel, grid, nwave * FF_WAVE, seg_bytes + sizeof(double) * (size_t)nwave * region, stream, B, nup, n, d, Z,
+                x, grad, lap, walker_state, nstates, centre, parts_out, parts_ws, magic, region, nwave * region / FF_ENERGY_PARTIAL,
+                (unsigned long long*)acc, ws);
+  FF_LAUNCH_CHECK();
+  if (nstates > 0) {
+    FF_LAUNCH(ff_energy_state_kernel, (unsigned)nstates, FF_RBLOCK(256), stream, B, walker_state, (const double*)parts_ws, centre, nstates,
+              (unsigned long long*)acc);
+    FF_LAUNCH_CHECK();
+  }
   return FF_OK;
 }
 

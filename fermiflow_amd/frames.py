@@ -2,7 +2,7 @@
 for a fresh batch of base walkers after the last iteration -- particles moving from the free-fermion base to the interacting state.
 `--frames_maps_out FILE.npz` writes the density maps (observables.DensityMaps) of the same walkers, one set per frame, binned on the
 device: without --frames_out no trajectory goes to the host.  The flags of the run's own maps (`--maps_out`) and of its one-body density
-matrix (`--obdm_out`, observables.OneBodyDensityMatrix) are declared here too."""
+matrix (`--obdm_out`, observables.OneBodyDensityMatrix) are declared here too, and `--energy_out` (observables.EnergyParts)."""
 import math
 
 import numpy as np
@@ -26,6 +26,8 @@ def add_arguments(parser):
     parser.add_argument("--obdm_sigma", type=float, default=1.0, help="width of the Gaussian the moved particle's position is drawn from")
     parser.add_argument("--obdm_every", type=int, default=1, help="measure the matrix on every obdm_every-th iteration")
     parser.add_argument("--obdm_stride", type=int, default=1, help="measure the matrix on every obdm_stride-th walker")
+    parser.add_argument("--energy_out", type=str, default=None,
+                        help=".npz file for the energy components (kinetic, trap, interaction by spin pair, virial) averaged over the run's iterations")
 
 
 def check_arguments(parser, args):
@@ -83,3 +85,27 @@ def write_obdm(args, model, rank):
         model.obdm.all_reduce_()
         if rank == 0:
             model.obdm.save_npz(args.obdm_out)
+
+
+def attach_energy(args, model, nup, ndown, device):
+    """--energy_out: the accumulator the sweeps of `model` feed (model.energy_parts); with a BetaVMC one state per many-body state."""
+    if args.energy_out:
+        from .observables import EnergyParts
+        es = getattr(model, "Es_original", None)
+        model.energy_parts = EnergyParts(nup, ndown, args.Z, dim=getattr(args, "dim", 2), nstates=0 if es is None else len(es), device=device)
+
+
+def energy_line(parts):
+    """E, T, V_trap, V_ee, the virial residual and dT, each with its walker-level error"""
+    m, e = parts.means(), parts.errors()
+    return "energy parts: " + "  ".join(f"{label} = {m[k]:.6f} +- {e[k]:.6f}" for label, k in
+                                        (("E", "E"), ("T", "T_L"), ("V_trap", "V_trap"), ("V_ee", "V_ee"), ("virial", "virial"), ("dT", "dT")))
+
+
+def write_energy(args, model, rank):
+    """After the last iteration: the sum over the ranks, then the file and one line on rank 0."""
+    if args.energy_out:
+        model.energy_parts.all_reduce_()
+        if rank == 0:
+            model.energy_parts.save_npz(args.energy_out)
+            print(energy_line(model.energy_parts))

@@ -581,6 +581,38 @@ def obdm_accumulate(nup, ndn, x, rprime, logp, sign, logp_moved, sign_moved, sig
                                        L.ptr(L.dev(acc, torch.int64, "acc")), L.ptr(L.dev(workspace, name="workspace"))), "ff_obdm_accumulate")
 
 
+# ---- energy components (include/fermiflow_energy.h, csrc/ff_energy_parts.h) -----------------------------
+def energy_parts_accumulate(nup, ndn, Z, x, grad, lap, walker_state, nstates, centre, parts_out, acc, workspace):
+    """ff_energy_parts_accumulate: one call = one block of the accumulator `acc` (int64 words, include/fermiflow_energy.h).  x, grad
+    (B, n, d) and lap (B) as eloc() leaves them; walker_state: sorted int32 (B) with nstates > 0, else None; centre: 6 doubles on the
+    device or None; parts_out: (B, 6) or None; `workspace`: fp64 scratch of at least ff_energy_parts_workspace_bytes(B, nstates) bytes."""
+    x = L.dev(x, name="x")
+    B, n, d = x.shape[0], nup + ndn, x.shape[2]
+    grad, lap = L.dev(grad, name="grad"), L.dev(lap, name="lap")
+    for v, shape, k in ((x, (B, n, d), "x"), (grad, (B, n, d), "grad"), (lap, (B,), "lap")):
+        if tuple(v.shape) != shape:
+            raise ValueError(f"energy_parts_accumulate: {k} must be {shape}, got {tuple(v.shape)}")
+    ws = None
+    if int(nstates) > 0:
+        if walker_state is None:
+            raise ValueError("energy_parts_accumulate: nstates > 0 needs walker_state")
+        ws = L.dev(_state(walker_state), torch.int32, "walker_state")
+        if tuple(ws.shape) != (B,):
+            raise ValueError(f"energy_parts_accumulate: walker_state must be ({B},), got {tuple(ws.shape)}")
+    if centre is not None:
+        centre = L.dev(centre, name="centre")
+        if centre.numel() != 6:
+            raise ValueError("energy_parts_accumulate: centre must hold 6 doubles")
+    if parts_out is not None and not (parts_out.is_cuda and parts_out.dtype == torch.float64 and parts_out.is_contiguous() and tuple(parts_out.shape) == (B, 6)):
+        raise ValueError(f"energy_parts_accumulate: parts_out must be a contiguous fp64 device tensor ({B}, 6)")
+    need = L.lib().ff_energy_parts_workspace_bytes(B, int(nstates))
+    if need and workspace.numel() * 8 < need:
+        raise ValueError(f"energy_parts_accumulate: workspace of {workspace.numel() * 8} bytes, {need} needed")
+    L.check(L.lib().ff_energy_parts_accumulate(L.stream(), B, nup, ndn, int(d), float(Z), L.ptr(x), L.ptr(grad), L.ptr(lap), L.ptr(ws), int(nstates),
+                                               L.ptr(centre), L.ptr(parts_out), L.ptr(L.dev(acc, torch.int64, "acc")),
+                                               L.ptr(L.dev(workspace, name="workspace"))), "ff_energy_parts_accumulate")
+
+
 # ---- d = 3 (csrc/ff_ho3d.hip) ---------------------------------------------------------------------------
 def logprob3d(tab_up, tab_dn, nup, ndn, x, walker_state=None, derivs=False):
     x = L.dev(x, name="x")

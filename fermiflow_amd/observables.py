@@ -23,6 +23,10 @@ frame rotating with the reference particle, through ff_maps_accumulate (csrc/ff_
 OneBodyDensityMatrix (at the end) is the off-diagonal one: the one-body reduced density matrix in the oscillator basis from
 wave-function ratios with one particle moved -- natural occupations, n(k) -- through ff_slater_sign and ff_obdm_accumulate
 (csrc/ff_obdm.h, include/fermiflow_obdm.h).
+
+EnergyParts (last) splits the energy: kinetic energy by two estimators, trap energy and the Coulomb repulsion by spin pair, their
+covariance, the virial residual and the energy of every many-body state, through ff_energy_parts_accumulate (csrc/ff_energy_parts.h,
+include/fermiflow_energy.h).
 """
 import math
 
@@ -607,4 +611,269 @@ class OneBodyDensityMatrix:
         for name in ("up", "down"):
             out["rho_" + name], out["err_" + name] = rho[name], err[name]
             out["occ_" + name], out["natorb_" + name] = occ[name]
+        np.savez(path, **out)
+
+
+# ---- energy components (include/fermiflow_energy.h, csrc/ff_energy_parts.h) -----------------------------------------------------
+ENERGY_NAMES = ("T_L", "T_G", "V_trap", "V_uu", "V_ud", "V_dd")
+# the derived quantities: linear in the six components, so their means and errors follow from the accumulated moments
+ENERGY_DERIVED = {"V_ee": (0, 0, 0, 1, 1, 1), "E": (1, 0, 1, 1, 1, 1), "virial": (2, 0, -2, 1, 1, 1), "dT": (1, -1, 0, 0, 0, 0)}
+ENERGY_MAX_STATES = 65536
+_EN_K, _EN_HEAD, _EN_FIXED = 6, 4, 52          # FF_ENERGY_PARTS, FF_ENERGY_HEAD, FF_ENERGY_FIXED
+
+
+class EnergyCounts(tuple):
+    """(calls, walkers, invalid) of an EnergyParts: blocks, valid walkers, walkers left out"""
+    __slots__ = ()
+    calls, walkers, invalid = (property(lambda self, i=i: self[i]) for i in range(3))
+
+
+class EnergyParts:
+    """How the energy of the walkers splits: the kinetic energy by two estimators (T_L = -1/2 laplacian psi / psi, T_G = 1/2 |grad ln psi|^2),
+    the trap energy V_trap and the Coulomb repulsion by spin pair (V_uu, V_ud, V_dd), their means, their covariance and, with nstates > 0,
+    the energy of every many-body state -- accumulated on the device from what the local-energy pass leaves (x, grad, lap).
+
+        parts = EnergyParts(nup, ndown, Z)                          # BetaVMC: nstates=len(model.Es_original)
+        model.energy_parts = parts           # GSVMC / BetaVMC: every sweep feeds it with one launch (two with states), right after the local-energy pass
+        ...
+        m, e = parts.means(), parts.errors(); m["virial"], e["virial"]; parts.dE_dZ(); parts.per_state()["E"]
+
+    Keys of means() / errors() / block_errors(): the six components and V_ee = V_uu + V_ud + V_dd, E = T_L + V_trap + V_ee, the virial
+    2 T_L - 2 V_trap + V_ee (zero on average in an eigenstate of the harmonic trap with Coulomb repulsion) and dT = T_L - T_G (zero on
+    average for any normalisable wave function).  errors() are walker-level standard errors -- the walkers of a sweep are independent
+    draws -- and those of the derived quantities come from the covariance of the components; block_errors() are block standard errors
+    with one block per call (NaN below two calls), for the six components only: the accumulator keeps no cross moments of the blocks, the
+    derived entries are NaN there.  Every variance is clamped at zero before its root, as E_std's: no NaN from rounding.
+
+    A walker with a component that is not finite (a failed integration, a coincident pair) is left out and counted.  `centre`: six
+    numbers near the expected means, about which the moments are taken (None: zeros); it is part of the object's identity, as Z is.
+    accumulate_raw() enqueues on torch's current stream and reads nothing on the host; the host reads the buffer only in counts() /
+    means() / ... / state_dict() / all_reduce_() / save_npz().  Every call must bring the same number of walkers.  A result is
+    bit-identical from run to run on one device.  all_reduce_() adds the sums of the ranks as doubles, once, when the run is over (the
+    counts are exact)."""
+
+    def __init__(self, nup, ndown, Z, dim=2, nstates=0, centre=None, device=None):
+        nup, ndown, Z, dim, nstates = int(nup), int(ndown), float(Z), int(dim), int(nstates)
+        if nup < 0 or ndown < 0 or nup + ndown < 1:
+            raise ValueError("EnergyParts: nup, ndown >= 0 and at least one particle")
+        if dim not in (2, 3):
+            raise ValueError("EnergyParts: dim must be 2 or 3")
+        if not math.isfinite(Z):
+            raise ValueError("EnergyParts: Z must be finite")
+        if nstates < 0:
+            raise ValueError("EnergyParts: nstates must not be negative")
+        if nup + ndown > 24 or (nup + ndown) * dim > 60:
+            raise NotImplementedError("EnergyParts: n <= 24 and n * dim <= 60")
+        if nstates > ENERGY_MAX_STATES:
+            raise NotImplementedError(f"EnergyParts: nstates <= {ENERGY_MAX_STATES}")
+        if centre is None:
+            ctr = (0.0,) * _EN_K
+        else:
+            ctr = tuple(float(v) for v in np.asarray(centre, dtype=np.float64).reshape(-1))
+            if len(ctr) != _EN_K or not all(math.isfinite(v) for v in ctr):
+                raise ValueError("EnergyParts: centre must be six finite numbers (T_L, T_G, V_trap, V_uu, V_ud, V_dd)")
+        self.nup, self.ndown, self.Z, self.dim, self.nstates, self.centre = nup, ndown, Z, dim, nstates, ctr
+        self._words = _EN_FIXED + 8 * nstates          # include/fermiflow_energy.h
+        self._B = None
+        self._buf = None
+        self._ws = None
+        self._ctr = None
+        self._checked = False
+        self.last = None
+        if device is not None:
+            self._buf = torch.zeros(self._words, dtype=torch.int64, device=torch.device(device))
+
+    # ---- device side -------------------------------------------------------------------------------------------------------
+    def accumulate_raw(self, x, grad, lap, walker_state=None):
+        """One ff_energy_parts_accumulate on the current stream: x (B, n, dim), grad (B, n, dim), lap (B), fp64 on the device, as native.eloc
+        leaves them; walker_state (B) int32, sorted, with nstates > 0.  One call is one block.  `last` keeps the (B, 6) components."""
+        from . import native
+        x = _lib.dev(x, name="x")
+        n = self.nup + self.ndown
+        if x.dim() != 3 or x.shape[1] != n or x.shape[2] != self.dim:
+            raise ValueError(f"EnergyParts.accumulate_raw: x must be (B, {n}, {self.dim}), got {tuple(x.shape)}")
+        if (walker_state is None) != (self.nstates == 0):
+            raise ValueError("EnergyParts.accumulate_raw: walker_state goes with nstates > 0, and only with it")
+        B = int(x.shape[0])
+        if self._B is not None and B != self._B:
+            raise ValueError(f"EnergyParts: {B} walkers, the earlier calls had {self._B} (the block errors need equal blocks)")
+        if self._buf is None or self._buf.device != x.device:
+            self._buf = torch.zeros(self._words, dtype=torch.int64, device=x.device) if self._buf is None else self._buf.to(x.device)
+        lib = _lib.lib()
+        if not self._checked:
+            if lib.ff_energy_parts_buffer_bytes(self.nstates) != 8 * self._words:
+                raise RuntimeError("EnergyParts: the library lays the accumulator out differently (include/fermiflow_energy.h)")
+            self._checked = True
+        need = max(1, lib.ff_energy_parts_workspace_bytes(B, self.nstates) // 8)
+        if self._ws is None or self._ws.device != x.device or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.float64, device=x.device)
+        if any(self.centre) and (self._ctr is None or self._ctr.device != x.device):
+            self._ctr = torch.tensor(self.centre, dtype=torch.float64, device=x.device)
+        last = torch.empty(B, _EN_K, dtype=torch.float64, device=x.device)
+        native.energy_parts_accumulate(self.nup, self.ndown, self.Z, x, grad, lap, walker_state, self.nstates, self._ctr, last, self._buf, self._ws)
+        self.last = last
+        if B > 0:
+            self._B = B
+
+    def check_hamiltonian(self, Z, use_ho, extra, nup, ndown, dim, nstates=None):
+        """The sweeps' guard: the components are those of the stock Hamiltonian -- harmonic trap and Coulomb repulsion of this object's Z --
+        for this object's particle numbers and dimension.  Nothing is decomposed under another one.  nstates: the sweep's state count
+        (None: a sweep without states); an object with per-state sums must have exactly that many."""
+        if self.nstates > 0 and nstates != self.nstates:
+            raise ValueError(f"energy_parts: the EnergyParts object has nstates = {self.nstates}, the sweep has {nstates or 'no'} states")
+        if extra or not use_ho:
+            raise ValueError("energy_parts: the components are those of HO() and CoulombPairPotential(Z); this model has other potentials")
+        if float(Z) != self.Z:
+            raise ValueError(f"energy_parts: the model's pair potential has Z = {Z}, the EnergyParts object Z = {self.Z}")
+        if (int(nup), int(ndown), int(dim)) != (self.nup, self.ndown, self.dim):
+            raise ValueError(f"energy_parts: the model has (nup, ndown, dim) = {(int(nup), int(ndown), int(dim))}, the EnergyParts object "
+                             f"{(self.nup, self.ndown, self.dim)}")
+
+    def reset(self):
+        if self._buf is not None:
+            self._buf.zero_()
+        self._B, self.last = None, None
+
+    def _int_words(self):
+        idx = list(range(3)) + list(range(_EN_FIXED, _EN_FIXED + self.nstates))
+        return torch.tensor(idx, dtype=torch.int64)
+
+    def all_reduce_(self):
+        """Sum calls, walkers, invalid and the states' counts (exact below 2^53, it raises otherwise) and every sum (doubles) over the ranks
+        of torch.distributed through dist.all_reduce_sum_.  Call it once, when the run is over: one block per rank and call."""
+        if self._buf is None:
+            self._buf = torch.zeros(self._words, dtype=torch.int64)
+        ii = self._int_words().to(self._buf.device)
+        isint = torch.zeros(self._words, dtype=torch.bool, device=self._buf.device)
+        isint[ii] = True
+        isint[3] = True                                  # (the ticket: zero between calls, not reduced)
+        fi = torch.nonzero(~isint).reshape(-1)
+        t = torch.cat([self._buf[ii].to(torch.float64), self._buf.view(torch.float64)[fi]])
+        D.all_reduce_sum_(t)
+        if bool((t[:ii.numel()] >= _EXACT).any()):
+            raise OverflowError("EnergyParts.all_reduce_: a count reached 2^53, the sum over ranks as doubles would not be exact")
+        self._buf[ii] = t[:ii.numel()].to(torch.int64)
+        self._buf.view(torch.float64)[fi] = t[ii.numel():]
+        return self
+
+    # ---- host side ---------------------------------------------------------------------------------------------------------
+    def _host(self):
+        a = np.zeros(self._words, dtype=np.int64) if self._buf is None else self._buf.cpu().numpy().astype(np.int64)
+        f = a.view(np.float64)
+        K, S = _EN_K, self.nstates
+        out = dict(calls=int(a[0]), walkers=int(a[1]), invalid=int(a[2]), sum=f[4:10].copy(), sum2=f[10:46].reshape(K, K).copy(), blocksq=f[46:52].copy())
+        if S > 0:
+            out.update(count=a[_EN_FIXED:_EN_FIXED + S].copy(), ssum=f[_EN_FIXED + S:_EN_FIXED + 7 * S].reshape(S, K).copy(),
+                       sumE2=f[_EN_FIXED + 7 * S:_EN_FIXED + 8 * S].copy())
+        return out
+
+    def counts(self):
+        """(calls, walkers, invalid): blocks, valid walkers, walkers that were left out"""
+        h = self._host()
+        return EnergyCounts((h["calls"], h["walkers"], h["invalid"]))
+
+    @staticmethod
+    def _combos():
+        c = {name: np.eye(_EN_K)[k] for k, name in enumerate(ENERGY_NAMES)}
+        c.update({name: np.array(a, dtype=np.float64) for name, a in ENERGY_DERIVED.items()})
+        return c
+
+    def _moments(self):
+        h = self._host()
+        N = float(h["walkers"])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m = h["sum"] / N
+            cov = h["sum2"] / N - np.outer(m, m)
+        return h, N, m, cov
+
+    def means(self):
+        """{name: mean over the valid walkers}"""
+        _, _, m, _ = self._moments()
+        c = np.asarray(self.centre) + m
+        return {name: float(a @ c) for name, a in self._combos().items()}
+
+    def cov(self):
+        """(6, 6): the covariance of the six components over the valid walkers (sum2 / N - mean mean^T about the centre), symmetric"""
+        return self._moments()[3]
+
+    def errors(self):
+        """{name: walker-level standard error sqrt(max(a^T cov a, 0) / (N - 1))}; NaN below two walkers"""
+        _, N, _, cov = self._moments()
+        out = {}
+        for name, a in self._combos().items():
+            with np.errstate(invalid="ignore"):
+                out[name] = float(np.sqrt(max(float(a @ cov @ a), 0.0) / (N - 1.0))) if N > 1 else float("nan")
+        return out
+
+    def block_errors(self):
+        """{name: block standard error, one block per call}: the six components from blocksq, NaN below two calls; NaN for the derived
+        entries (no cross moments of the blocks are kept)"""
+        h = self._host()
+        out = dict.fromkeys(list(ENERGY_NAMES) + list(ENERGY_DERIVED), float("nan"))
+        if h["calls"] >= 2:
+            m = float(h["calls"])
+            var = np.maximum(h["blocksq"] / m - (h["sum"] / m) ** 2, 0.0) * (m / (m - 1.0))
+            with np.errstate(divide="ignore", invalid="ignore"):
+                err = np.sqrt(var / m) / (float(h["walkers"]) / m)
+            out.update({name: float(err[k]) for k, name in enumerate(ENERGY_NAMES)})
+        return out
+
+    def dE_dZ(self):
+        """(value, error) of the Hellmann-Feynman derivative dE/dZ = <V_ee> / Z; NaN at Z = 0"""
+        if self.Z == 0.0:
+            return float("nan"), float("nan")
+        return self.means()["V_ee"] / self.Z, self.errors()["V_ee"] / abs(self.Z)
+
+    def per_state(self):
+        """{"count" (S,), the six names (S,): means over the state's valid walkers, "E" (S,), "E_err" (S,): its walker-level standard
+        error (NaN below two walkers)}; NaN where a state drew no walker"""
+        if self.nstates == 0:
+            raise ValueError("EnergyParts.per_state: this object has nstates = 0")
+        h = self._host()
+        cnt = h["count"].astype(np.float64)
+        ctr = np.asarray(self.centre)
+        e_idx = [k for k, a in enumerate(ENERGY_DERIVED["E"]) if a]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d = h["ssum"] / cnt[:, None]
+            out = {"count": h["count"].copy()}
+            out.update({name: ctr[k] + d[:, k] for k, name in enumerate(ENERGY_NAMES)})
+            dE = d[:, e_idx].sum(1)
+            out["E"] = ctr[e_idx].sum() + dE
+            var = np.maximum(h["sumE2"] / cnt - dE * dE, 0.0)
+            out["E_err"] = np.where(cnt > 1, np.sqrt(var / np.where(cnt > 1, cnt - 1.0, 1.0)), np.nan)
+        return out
+
+    def state_dict(self):
+        acc = torch.zeros(self._words, dtype=torch.int64) if self._buf is None else self._buf.cpu().clone()
+        return {"nup": self.nup, "ndown": self.ndown, "Z": self.Z, "dim": self.dim, "nstates": self.nstates, "centre": self.centre, "acc": acc}
+
+    def load_state_dict(self, st):
+        for k in ("nup", "ndown", "Z", "dim", "nstates"):
+            if st[k] != getattr(self, k):
+                raise ValueError(f"EnergyParts.load_state_dict: {k} = {st[k]!r}, this object has {getattr(self, k)!r}")
+        if tuple(float(v) for v in st["centre"]) != self.centre:
+            raise ValueError(f"EnergyParts.load_state_dict: centre = {tuple(st['centre'])!r}, this object has {self.centre!r}")
+        acc = torch.as_tensor(st["acc"]).to(torch.int64).reshape(-1)
+        if acc.numel() != self._words:
+            raise ValueError(f"EnergyParts.load_state_dict: {acc.numel()} words, expected {self._words}")
+        if self._buf is None:
+            self._buf = torch.zeros(self._words, dtype=torch.int64)
+        self._buf.copy_(acc.to(self._buf.device))
+        calls, total = int(acc[0]), int(acc[1]) + int(acc[2])
+        self._B = total // calls if calls > 0 else None
+
+    def save_npz(self, path):
+        """One .npz (what the drivers' --energy_out writes): names, mean, err, block_err (one entry per name, the six components and the
+        four derived quantities), cov, dE_dZ, the raw moments, the counts, the per-state table with nstates > 0 and the settings."""
+        h = self._host()
+        names = list(ENERGY_NAMES) + list(ENERGY_DERIVED)
+        m, e, b = self.means(), self.errors(), self.block_errors()
+        out = dict(names=np.array(names), mean=np.array([m[k] for k in names]), err=np.array([e[k] for k in names]),
+                   block_err=np.array([b[k] for k in names]), cov=self.cov(), dE_dZ=np.array(self.dE_dZ()), sum=h["sum"], sum2=h["sum2"],
+                   blocksq=h["blocksq"], calls=h["calls"], walkers=h["walkers"], invalid=h["invalid"], centre=np.asarray(self.centre),
+                   nup=self.nup, ndown=self.ndown, Z=self.Z, dim=self.dim, nstates=self.nstates)
+        if self.nstates > 0:
+            ps = self.per_state()
+            out.update(state_count=ps["count"], state_E=ps["E"], state_E_err=ps["E_err"], state_mean=np.stack([ps[k] for k in ENERGY_NAMES], axis=1),
+                       state_sum=h["ssum"], state_sumE2=h["sumE2"])
         np.savez(path, **out)
