@@ -14,7 +14,7 @@ import time
 
 import torch
 
-from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, DensityMaps, Observables, checkpoint, frames, native
+from . import HO2D, HO3D, FreeFermion, MLP, Backflow, CNF, HO, CoulombPairPotential, GSVMC, DMC, DensityMaps, Observables, checkpoint, frames, native
 from .sr import SR
 from .utils import make_adam
 
@@ -50,7 +50,32 @@ def build_parser():
                         help="robust estimator (not in the reference): drop failed walkers and clip the local energies to their median "
                              "+- K mean absolute deviations before the gradient is formed; not with --optimizer sr")
     frames.add_arguments(parser)
+    parser.add_argument("--dmc_blocks", type=int, default=0,
+                        help="fixed-node diffusion Monte Carlo with the trained flow as guiding function (not in the reference): number of "
+                             "measured blocks, run after the training on --batch walkers (0: off); one rank, --dim 2")
+    parser.add_argument("--dmc_tau", type=float, default=0.01, help="time step of --dmc_blocks")
+    parser.add_argument("--dmc_steps", type=int, default=50, help="steps per block of --dmc_blocks")
+    parser.add_argument("--dmc_equil", type=int, default=2, help="blocks of --dmc_blocks that equilibrate and are not measured")
+    parser.add_argument("--dmc_seed", type=int, default=0, help="Philox key of --dmc_blocks (proposals, accept uniforms, comb offsets)")
+    parser.add_argument("--dmc_drift_limit", type=float, default=1.0, help="a of the limited drift of --dmc_blocks (0: the plain drift)")
+    parser.add_argument("--dmc_ecut", type=float, default=0.2,
+                        help="the weights of --dmc_blocks see the local energies clipped to E_ref +- ecut sqrt(n / tau)")
+    parser.add_argument("--dmc_out", type=str, default=None, metavar="FILE.npz", help="write the result of --dmc_blocks here")
     return parser
+
+
+def run_dmc(args, model):
+    """--dmc_blocks: E_VMC of the population, E_DMC +- its error and the diagnostics; --dmc_out: the same as an .npz"""
+    dmc = DMC(model, tau=args.dmc_tau, steps_per_block=args.dmc_steps, drift_limit=args.dmc_drift_limit, ecut=args.dmc_ecut, seed=args.dmc_seed)
+    dmc.start(args.batch)
+    r = dmc.run(args.dmc_blocks, equilibrate=args.dmc_equil)
+    print("DMC: tau = %g, %d + %d blocks of %d steps, %d walkers" % (args.dmc_tau, args.dmc_equil, args.dmc_blocks, args.dmc_steps, args.batch))
+    print("E_VMC:", r["E_vmc"], "E_DMC:", r["E"], "+-", r["E_err"])
+    print("acceptance:", r["acceptance"], "node crossings:", r["crossing"], "invalid:", r["invalid"], "effective sample fraction:", r["esf"],
+          "distinct sources per comb:", r["distinct"])
+    if args.dmc_out:
+        dmc.save_npz(args.dmc_out)
+    return r
 
 
 def make_optimizer(args, model):
@@ -65,6 +90,12 @@ def main(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     frames.check_arguments(parser, args)
+    if args.dmc_blocks < 0:
+        parser.error("--dmc_blocks must be >= 0")
+    if args.dmc_blocks and (args.dmc_equil < 0 or args.dmc_steps < 1 or not args.dmc_tau > 0 or args.dmc_drift_limit < 0 or not args.dmc_ecut > 0):
+        parser.error("--dmc_equil and --dmc_drift_limit must be >= 0, --dmc_steps >= 1, --dmc_tau and --dmc_ecut > 0")
+    if args.dmc_blocks and (args.dim != 2 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        parser.error("--dmc_blocks needs --dim 2 and a single rank")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -131,6 +162,8 @@ def main(argv=None):
             model.density_maps.save_npz(args.maps_out)
     frames.write_obdm(args, model, rank)
     frames.write_energy(args, model, rank)
+    if args.dmc_blocks:
+        run_dmc(args, model)
     if (args.frames_out or args.frames_maps_out) and rank == 0:
         z = basedist.sample(model.orbitals_up, model.orbitals_down, (args.frames_batch,))
         frames.write(args, cnf.generate(z, nframes=args.nframes), cnf.t_span, args.nup, args.ndown, args.dim)

@@ -19,5 +19,6 @@ from .VMC import GSVMC, BetaVMC                         # noqa: E402,F401
 from .utils import y_grad_laplacian                     # noqa: E402,F401
 from .NeuralODE.nnModule import solve_ivp_nnmodule      # noqa: E402,F401
 from .observables import DensityMaps, EnergyParts, Observables, OneBodyDensityMatrix                    # noqa: E402,F401
+from .dmc import DMC                                    # noqa: E402,F401
 from .sr import SR, BetaSR                              # noqa: E402,F401
 from . import checkpoint                                # noqa: E402,F401

@@ -1,5 +1,5 @@
 """The C ABI of include/fermiflow.h (and of include/fermiflow_robust.h: ROBUST_SIGNATURES; include/fermiflow_maps.h: MAPS_SIGNATURES;
-include/fermiflow_obdm.h: OBDM_SIGNATURES; include/fermiflow_energy.h: ENERGY_SIGNATURES) as ctypes sees it: its three structs and the
+include/fermiflow_obdm.h: OBDM_SIGNATURES; include/fermiflow_energy.h: ENERGY_SIGNATURES; include/fermiflow_dmc.h: DMC_SIGNATURES) as ctypes sees it: its three structs and the
 signature of every function, declared once.
 fermiflow_amd._lib binds libfermiflow_hip.so to this table and tests/hostsim/simlib.py the host simulator's build of the same sources;
 tests/test_host_logic.py holds the table to the header, prototype by prototype.  Imports nothing but ctypes."""
@@ -112,12 +112,22 @@ ENERGY_SIGNATURES = {
 # FF_ENERGY_PARTS, FF_ENERGY_CHUNK, FF_ENERGY_PARTIAL, FF_ENERGY_HEAD, FF_ENERGY_FIXED, FF_ENERGY_MAX_STATES
 ENERGY_PARTS, ENERGY_CHUNK, ENERGY_PARTIAL, ENERGY_HEAD, ENERGY_FIXED, ENERGY_MAX_STATES = 6, 256, 28, 4, 52, 65536
 
+# include/fermiflow_dmc.h, the sixth public header (fixed-node diffusion Monte Carlo), in its order
+DMC_SIGNATURES = {
+    "ff_dmc_propose": (_I, (_P, _Q, _I, _I, _I, _D, _D, _P, _P, _P, _U, _Q, _Q, _P, _P)),
+    "ff_dmc_accept_workspace_bytes": (_Z, (_Q,)),
+    "ff_dmc_accept": (_I, (_P, _Q, _I, _I, _I, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U, _Q, _Q, _P, _P, _Q, _P, _I, _P)),
+    "ff_dmc_comb_workspace_bytes": (_Z, (_Q,)),
+    "ff_dmc_comb": (_I, (_P, _Q, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _U, _Q, _P, _P, _P, _P, _P, _P, _P, _P)),
+}
+DMC_REC, DMC_CHUNK, DMC_U_SLOT = 9, 256, 64      # FF_DMC_REC, FF_DMC_CHUNK, FF_DMC_U_SLOT
+
 
 def bind(cdll):
-    """Set restype and argtypes of every function of SIGNATURES, ROBUST_SIGNATURES, MAPS_SIGNATURES, OBDM_SIGNATURES and ENERGY_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
+    """Set restype and argtypes of every function of SIGNATURES, ROBUST_SIGNATURES, MAPS_SIGNATURES, OBDM_SIGNATURES, ENERGY_SIGNATURES and DMC_SIGNATURES that `cdll` exports; returns cdll.  One it lacks (the
     host simulator has no ff_comm_*; an A/B build of an earlier commit may lack the newest) is skipped and fails where it is called, as
     any missing symbol."""
-    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES, **MAPS_SIGNATURES, **OBDM_SIGNATURES, **ENERGY_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **ROBUST_SIGNATURES, **MAPS_SIGNATURES, **OBDM_SIGNATURES, **ENERGY_SIGNATURES, **DMC_SIGNATURES}.items():
         fn = getattr(cdll, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = restype, argtypes

@@ -8,7 +8,7 @@ import os
 
 import torch
 
-from ._abi import ABI_VERSION, ROBUST_NSTAT, ROBUST_SIGNATURES, SIGNATURES, FFKernelPlanInfo, FFNet, FFOde, bind, ode_struct  # noqa: F401 (the structs are part of this module's surface)
+from ._abi import ABI_VERSION, DMC_REC, ROBUST_NSTAT, ROBUST_SIGNATURES, SIGNATURES, FFKernelPlanInfo, FFNet, FFOde, bind, ode_struct  # noqa: F401 (the structs are part of this module's surface)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FERMIFLOW_LIB") or os.path.join(_HERE, "libfermiflow_hip.so")   # env: A/B builds in tools/

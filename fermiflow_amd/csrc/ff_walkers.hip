@@ -684,6 +684,8 @@ ff_beta_finish_kernel(const double* __restrict__ buf, const double* __restrict__
 #include "ff_obdm.h"
 // energy components of the physical walkers: kinetic by two estimators, trap, Coulomb repulsion by spin pair (include/fermiflow_energy.h)
 #include "ff_energy_parts.h"
+// fixed-node diffusion Monte Carlo on the trained wave function: proposals, accept step with weights, comb (include/fermiflow_dmc.h)
+#include "ff_dmc.h"
 // the opt-in robust estimator: median by radix select, clipped local energies, gradient weights (ff_energy_robust, include/fermiflow_robust.h)
 #include "ff_robust.h"
 
@@ -1425,6 +1427,82 @@ int ff_energy_parts_accumulate(void* stream, int64_t B, int nup, int ndn, int d,
               (unsigned long long*)acc);
     FF_LAUNCH_CHECK();
   }
+  return FF_OK;
+}
+
+// what the three ff_dmc_* calls refuse alike
+static inline int ff_dmc_check(int64_t B, int nup, int ndn, int d, bool ptrs_ok) {
+  if (!(B >= 0 && nup >= 0 && ndn >= 0 && (int64_t)nup + ndn >= 1 && d >= 1 && (B == 0 || ptrs_ok))) return ff_refuse(FF_EINVAL, "ff_dmc", "bad argument");
+  if (d != 2) return ff_refuse(FF_EUNSUPPORTED, "ff_dmc", "d must be 2");
+  if ((int64_t)nup + ndn > FF_MAX_N) return ff_refuse(FF_EUNSUPPORTED, "ff_dmc", "n > 24");
+  if (const int st = ff_check_det_size("ff_dmc", nup, ndn)) return st;
+  if (B >= ((int64_t)1 << 31)) return ff_refuse(FF_EUNSUPPORTED, "ff_dmc", "B >= 2^31");
+  return FF_OK;
+}
+static inline bool ff_dmc_step_ok(int64_t step) { return step >= 0 && step < ((int64_t)1 << 32); }
+
+int ff_dmc_propose(void* stream, int64_t B, int nup, int ndn, int d, double tau, double drift_limit, const double* x, const double* grad,
+                   const double* noise, uint64_t seed, int64_t walker_offset, int64_t step, double* x_new, double* xi_out) {
+  FF_CHECK(tau > 0.0 && tau <= 1.7976931348623157e308, FF_EINVAL, "ff_dmc: tau must be positive and finite");
+  FF_CHECK(drift_limit >= 0.0 && drift_limit <= 1.7976931348623157e308, FF_EINVAL, "ff_dmc: drift_limit must be finite and >= 0");
+  FF_CHECK(ff_dmc_step_ok(step) && walker_offset >= 0, FF_EINVAL, "ff_dmc: step outside [0, 2^32) or walker_offset < 0");
+  if (const int st = ff_dmc_check(B, nup, ndn, d, x && grad && x_new)) return st;
+  if (B == 0) return FF_OK;
+  const int n = nup + ndn, Q = (n + 1) / 2;
+  FF_LAUNCH(ff_dmc_propose_kernel, ff_grid(B * Q, 256), 256, stream, B, n, Q, tau, sqrt(tau), (2.0 * drift_limit) * tau, x, grad, noise, seed,
+            (uint64_t)walker_offset, (uint32_t)step, x_new, xi_out);
+  FF_LAUNCH_CHECK();
+  return FF_OK;
+}
+
+size_t ff_dmc_accept_workspace_bytes(int64_t B) {
+  if (B < 0 || B >= ((int64_t)1 << 31)) return 0;
+  const size_t nchunks = B > 0 ? (size_t)((B + FF_DMC_CHUNK - 1) / FF_DMC_CHUNK) : 1;
+  return sizeof(double) * (1 + FF_DMC_REC * nchunks);
+}
+
+int ff_dmc_accept(void* stream, int64_t B, int nup, int ndn, int d, double tau, double drift_limit, double* x, double* logp, double* grad,
+                  double* eloc, double* sign, double* w, const double* x_new, const double* logp_new, const double* grad_new,
+                  const double* eloc_new, const double* sign_new, const double* u, uint64_t seed, int64_t walker_offset, int64_t step,
+                  const double* ctrl, void* rec, int64_t step_slot, uint8_t* accepted_out, int groups, void* workspace) {
+  FF_CHECK(tau > 0.0 && tau <= 1.7976931348623157e308, FF_EINVAL, "ff_dmc: tau must be positive and finite");
+  FF_CHECK(drift_limit >= 0.0 && drift_limit <= 1.7976931348623157e308, FF_EINVAL, "ff_dmc: drift_limit must be finite and >= 0");
+  FF_CHECK(ff_dmc_step_ok(step) && walker_offset >= 0 && step_slot >= 0, FF_EINVAL, "ff_dmc: step outside [0, 2^32), walker_offset or step_slot < 0");
+  FF_CHECK(groups >= 0 && groups <= 65536, FF_EINVAL, "ff_dmc: groups outside [0, 65536]");
+  if (const int st = ff_dmc_check(B, nup, ndn, d, x && logp && grad && eloc && sign && w && x_new && logp_new && grad_new && eloc_new && sign_new &&
+                                                   ctrl && rec && workspace)) return st;
+  if (B == 0) return FF_OK;
+  const int64_t nchunks = (B + FF_DMC_CHUNK - 1) / FF_DMC_CHUNK;
+  const unsigned grid = ff_grid(nchunks, 1, groups > 0 ? groups : ff_device_cus() * FF_DMC_GRID_PER_CU);
+  FF_LAUNCH(ff_dmc_accept_kernel, grid, FF_DMC_CHUNK, stream, B, nup + ndn, tau, (2.0 * drift_limit) * tau, x, logp, grad, eloc, sign, w, x_new,
+            logp_new, grad_new, eloc_new, sign_new, u, seed, (uint64_t)walker_offset, (uint32_t)step, ctrl,
+            (double*)rec + step_slot * FF_DMC_REC, accepted_out, (unsigned long long*)workspace);
+  FF_LAUNCH_CHECK();
+  return FF_OK;
+}
+
+size_t ff_dmc_comb_workspace_bytes(int64_t B) {
+  if (B < 0 || B >= ((int64_t)1 << 31)) return 0;
+  const size_t nchunks = B > 0 ? (size_t)((B + FF_DMC_CHUNK - 1) / FF_DMC_CHUNK) : 1;
+  return sizeof(double) * (FF_DMC_HEAD + (size_t)B + 3 * nchunks);
+}
+
+int ff_dmc_comb(void* stream, int64_t B, int nup, int ndn, int d, double* w, const double* x, const double* logp, const double* grad,
+                const double* eloc, const double* sign, const double* u0, uint64_t seed, int64_t step, int32_t* src, double* x_out,
+                double* logp_out, double* grad_out, double* eloc_out, double* sign_out, int32_t* info, void* workspace) {
+  FF_CHECK(ff_dmc_step_ok(step), FF_EINVAL, "ff_dmc: step outside [0, 2^32)");
+  if (const int st = ff_dmc_check(B, nup, ndn, d, w && x && logp && grad && eloc && sign && src && x_out && logp_out && grad_out && eloc_out &&
+                                                   sign_out && info && workspace)) return st;
+  if (B == 0) return FF_OK;
+  const int64_t nchunks = (B + FF_DMC_CHUNK - 1) / FF_DMC_CHUNK;
+  const int64_t cap = ff_device_cus() * FF_DMC_GRID_PER_CU;
+  FF_LAUNCH(ff_dmc_cum_kernel, ff_grid(nchunks, 1, cap), FF_DMC_CHUNK, stream, B, (const double*)w, info, (unsigned long long*)workspace);
+  FF_LAUNCH_CHECK();
+  FF_LAUNCH(ff_dmc_resample_kernel, ff_grid(B, 256, cap), 256, stream, B, 2 * (nup + ndn), w, x, logp, grad, eloc, sign, u0, seed, (uint32_t)step,
+            src, x_out, logp_out, grad_out, eloc_out, sign_out, (const unsigned long long*)workspace);
+  FF_LAUNCH_CHECK();
+  FF_LAUNCH(ff_dmc_comb_stats_kernel, ff_grid(B, 256, cap), 256, stream, B, (const int*)src, info);
+  FF_LAUNCH_CHECK();
   return FF_OK;
 }
 

@@ -613,6 +613,89 @@ def energy_parts_accumulate(nup, ndn, Z, x, grad, lap, walker_state, nstates, ce
                                                L.ptr(L.dev(workspace, name="workspace"))), "ff_energy_parts_accumulate")
 
 
+# ---- fixed-node diffusion Monte Carlo (include/fermiflow_dmc.h, csrc/ff_dmc.h) ---------------------------
+DMC_REC = L.DMC_REC      # 8-byte words of a step's record
+_DMC_STATE = ("x", "logp", "grad", "eloc", "sign")
+
+
+def _dmc_fields(who, d, B, n, names=_DMC_STATE):
+    out = []
+    for k in names:
+        v = L.dev(d[k], name=f"{who}[{k}]")
+        shape = (B, n, 2) if k in ("x", "grad") else (B,)
+        if tuple(v.shape) != shape or v.data_ptr() != d[k].data_ptr():
+            raise ValueError(f"{who}[{k}] must be a contiguous fp64 device tensor {shape}, got {tuple(d[k].shape)}")
+        out.append(v)
+    return out
+
+
+def dmc_workspaces(B, device):
+    """the zeroed workspaces of dmc_accept and dmc_comb for B walkers (their first word is a ticket the kernels leave at zero)"""
+    f = dict(dtype=torch.float64, device=device)
+    return (torch.zeros(max(1, L.lib().ff_dmc_accept_workspace_bytes(B) // 8), **f),
+            torch.zeros(max(1, L.lib().ff_dmc_comb_workspace_bytes(B) // 8), **f))
+
+
+def dmc_propose(nup, ndn, x, grad, tau, drift_limit, noise=None, seed=0, walker_offset=0, step=0, want_xi=False, out=None):
+    """ff_dmc_propose: x' = x + tau vbar + sqrt(tau) xi; (x', xi or None).  noise: explicit normals (B, n, 2), else Philox at
+    (seed, walker_offset + b, step)."""
+    x, grad = L.dev(x, name="x"), L.dev(grad, name="grad")
+    B, n = x.shape[0], nup + ndn
+    noise = L.dev(noise, name="noise") if noise is not None else None
+    for v, k in ((x, "x"), (grad, "grad")) + (((noise, "noise"),) if noise is not None else ()):
+        if tuple(v.shape) != (B, n, 2):
+            raise ValueError(f"dmc_propose: {k} must be ({B}, {n}, 2), got {tuple(v.shape)}")
+    xn = torch.empty_like(x) if out is None else out
+    xi = torch.empty_like(x) if want_xi else None
+    L.check(L.lib().ff_dmc_propose(L.stream(), B, nup, ndn, 2, float(tau), float(drift_limit), L.ptr(x), L.ptr(grad),
+                                   L.ptr(noise), int(seed), int(walker_offset), int(step), L.ptr(xn),
+                                   L.ptr(xi)), "ff_dmc_propose")
+    return xn, xi
+
+
+def dmc_accept(nup, ndn, state, prop, tau, drift_limit, ctrl, rec, step_slot, workspace, u=None, seed=0, walker_offset=0, step=0,
+               want_mask=False, groups=0):
+    """ff_dmc_accept: state = dict x, logp, grad, eloc, sign, w (overwritten in place), prop = dict x ... sign of the proposals; ctrl: 3
+    device doubles (E_T, E_ref, c); rec: int64 or fp64 device words, the record goes to words [9 step_slot, 9 step_slot + 9).
+    Returns the uint8 accept mask if asked for."""
+    B, n = state["x"].shape[0], nup + ndn
+    s = _dmc_fields("state", state, B, n, _DMC_STATE + ("w",))
+    q = _dmc_fields("prop", prop, B, n)
+    ctrl = L.dev(ctrl, name="ctrl")
+    if ctrl.numel() != 3 or rec.element_size() != 8 or not rec.is_cuda or not rec.is_contiguous() or rec.numel() < DMC_REC * (int(step_slot) + 1):
+        raise ValueError("dmc_accept: ctrl must hold 3 doubles and rec 9 (step_slot + 1) contiguous 8-byte device words")
+    need = L.lib().ff_dmc_accept_workspace_bytes(B)
+    if workspace.numel() * 8 < need:
+        raise ValueError(f"dmc_accept: workspace of {workspace.numel() * 8} bytes, {need} needed")
+    u = L.dev(u, name="u") if u is not None else None
+    if u is not None and tuple(u.shape) != (B,):
+        raise ValueError(f"dmc_accept: u must be ({B},)")
+    mask = torch.empty(B, dtype=torch.uint8, device=s[0].device) if want_mask else None
+    L.check(L.lib().ff_dmc_accept(L.stream(), B, nup, ndn, 2, float(tau), float(drift_limit), *[L.ptr(v) for v in s], *[L.ptr(v) for v in q],
+                                  L.ptr(u), int(seed), int(walker_offset), int(step), L.ptr(ctrl), L.ptr(rec),
+                                  int(step_slot), L.ptr(mask), int(groups), L.ptr(L.dev(workspace, name="workspace"))), "ff_dmc_accept")
+    return mask
+
+
+def dmc_comb(nup, ndn, state, out, src, info, workspace, u0=None, seed=0, step=0):
+    """ff_dmc_comb: the state (dict x ... sign, w) resampled into `out` (dict x ... sign, other buffers); state["w"] becomes 1; src int32
+    (B) and info int32 (4: distinct sources, largest copy count, flag, 0) are written."""
+    B, n = state["x"].shape[0], nup + ndn
+    s = _dmc_fields("state", state, B, n, _DMC_STATE + ("w",))
+    o = _dmc_fields("out", out, B, n)
+    if any(a.data_ptr() == b.data_ptr() for a, b in zip(s, o)):
+        raise ValueError("dmc_comb: the output buffers must not be the input buffers")
+    src, info = L.dev(src, torch.int32, "src"), L.dev(info, torch.int32, "info")
+    if src.numel() != B or info.numel() != 4:
+        raise ValueError("dmc_comb: src must hold B and info 4 int32 words")
+    need = L.lib().ff_dmc_comb_workspace_bytes(B)
+    if workspace.numel() * 8 < need:
+        raise ValueError(f"dmc_comb: workspace of {workspace.numel() * 8} bytes, {need} needed")
+    L.check(L.lib().ff_dmc_comb(L.stream(), B, nup, ndn, 2, L.ptr(s[5]), *[L.ptr(v) for v in s[:5]], L.ptr(L.dev(u0, name="u0") if u0 is not None else None),
+                                int(seed), int(step), L.ptr(src), *[L.ptr(v) for v in o], L.ptr(info), L.ptr(L.dev(workspace, name="workspace"))),
+            "ff_dmc_comb")
+
+
 # ---- d = 3 (csrc/ff_ho3d.hip) ---------------------------------------------------------------------------
 def logprob3d(tab_up, tab_dn, nup, ndn, x, walker_state=None, derivs=False):
     x = L.dev(x, name="x")
